@@ -11,8 +11,21 @@ NF4->bf16 (configs[1]).  A *step* is one pass of the hot path over one batch:
   batched launch (``nf4_dequant_ref_batched``); strong scaling (the 8-matrix job
   is fixed).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline needs and no more: setup, warmup, the timed regions,
+the result line.  ``--full`` adds everything else this file measures or checks, each a
+run of its own: the oracle check of step 0's output, the memory-system twin
+(``roofline.twin``), the ``c5`` object and the CPU baselines (``cpu_baseline``,
+``c5.cpu_baseline``); ``--no-ceiling``, ``--no-c5`` and ``--no-cpu-baseline`` drop single
+parts of it.  Without ``--full`` those keys are on the line as ``null``.
+
+``--dump-outputs DIR`` writes, after the timed regions, what the last timed step left in
+its output set -- the arrays a caller of the C ABI receives -- as ``DIR/out_matrix<id>.npy``
+in float32, one file per matrix of this rank (<id> = the global matrix id).  At most 48 MiB
+are written in all; a larger matrix is cut to a fixed, seeded sample of its rows.  The
+inputs are seeded, so two builds run with the same arguments can be compared file by file.
 
 ``--gpus N`` without a launcher (WORLD_SIZE unset) spawns N fresh rank processes
 before this process touches the GPU and relays rank 0's line; under a launcher
@@ -23,7 +36,9 @@ each K eager launches of the product C-ABI entry (``nf4_dequant_ref``, arguments
 prepared up front), bracketed by barrier + synchronize on both sides, HIP events on the
 launch stream around them.  Per region the max over ranks counts; the region with the
 median of those maxima is the result (median, not one sample), and every
-region's figure is on the line (``repeats``).  Ahead of each start event sit L = 16
+region's figure is on the line (``repeats``).  On one rank no further region starts once
+the regions so far took 1 s together: the repeats are there against the noise of short
+regions, and a run with a large K is not made 7 times as long for them.  Ahead of each start event sit L = 16
 untimed launches of the preceding buffer sets, so the queue holds real work when
 timing starts, as in a steady stream of weights, and ahead of those a device spin that
 outlasts the host's submission of all L + K launches (``--lead spin-steps``): the K
@@ -59,7 +74,7 @@ interleave), so it bounds nothing.  ``measured_copy_peak``:
 guide's measured float4-copy rate (6.29 TB/s, MI355X_MICROARCH.md) beside the 8 TB/s
 spec, and ``frac_of_measured_copy`` the headline against it.
 
-CPU baseline (``cpu_baseline``, rank 0 at N=1), same workload on this GPU's
+CPU baseline (``cpu_baseline``, rank 0, with ``--full``), same workload on this GPU's
 host share of cores (at most 16): ``value`` = oracle/fallback_torch.py, a
 torch-CPU restatement with the reference fallback's loop structure (the CPU path
 the reference itself runs, bit-equal to it); ``native`` = this library's own
@@ -107,6 +122,8 @@ ROUNDS = ("r06", "r05", "r04", "r03", "r02", "r01")  # profiles/<round>/pmc_traf
 MIN_READ_FOOTPRINT = 512 << 20
 MIN_WRITE_FOOTPRINT = 512 << 20
 C5_MIN_STEPS = 100  # the c5 object's timed steps at least (its launches are 27-215 us)
+REGION_BUDGET_MS = 1000.0  # one rank: no further timed region once the regions so far took this long
+DUMP_MAX_BYTES = 48 << 20  # --dump-outputs: float32 bytes written, all ranks and matrices together
 
 
 def log(*a):
@@ -119,6 +136,12 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="c2", choices=["c2", "c5"])
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the oracle check of step 0, the memory-system twin, the c5 "
+                         "object and the CPU baselines (each a run of its own; off by default)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs to DIR/out_matrix<id>.npy (float32; matrices "
+                         "past the size limit as a fixed, seeded sample of their rows)")
     ap.add_argument("--m", type=int, default=None, help="override the c2 matrix shape (rows)")
     ap.add_argument("--n", type=int, default=None, help="override the c2 matrix shape (columns)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
@@ -457,7 +480,8 @@ class Workload:
 
 def time_steps(args, wl, dev, world, graph_ok=True):
     """Warmup, one untimed pass over every buffer set, then ``--repeats`` timed regions
-    of exactly K steps each (see the module docstring), every region bracketed by a
+    of exactly K steps each (fewer on one rank once they took REGION_BUDGET_MS together;
+    see the module docstring), every region bracketed by a
     barrier + synchronize on both sides; returns ([ms for K steps on this rank, one per
     region], launch mode)."""
     import torch
@@ -506,6 +530,8 @@ def time_steps(args, wl, dev, world, graph_ok=True):
         ev0 = torch.cuda.Event(enable_timing=True)
         ev1 = torch.cuda.Event(enable_timing=True)
     for _rep in range(max(1, args.repeats)):
+        if world == 1 and sum(times) >= REGION_BUDGET_MS:
+            break  # long regions need no 7 repeats (several ranks keep R: they must agree on it)
         if world > 1:
             dist.barrier()
         if not cpu:
@@ -570,6 +596,25 @@ def median_region(my_times, dev, world):
     order = sorted(range(R), key=lambda i: maxima[i])
     pick = order[(R - 1) // 2]  # the lower median for even R: always one measured region
     return maxima[pick], [table[r][pick] for r in range(world)], maxima
+
+
+def dump_outputs(wl, step, dirname, n_arrays):
+    """--dump-outputs: the output set that timed step ``step`` wrote, one
+    ``out_matrix<global id>.npy`` per matrix of this rank, float32 (exact for bf16 and
+    fp16).  ``n_arrays`` matrices of all ranks share DUMP_MAX_BYTES; a matrix past its
+    share is cut to a seeded sample of its rows, ascending, the same in every run."""
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(1, n_arrays)
+    for (gid, m, n), out in zip(wl.mats, wl.outs[step % wl.Pout]):
+        rows = min(m, max(1, budget // (4 * n)))
+        if rows < m:
+            idx = np.sort(np.random.default_rng(3409).choice(m, rows, replace=False))
+            out = out[torch.from_numpy(idx).to(out.device)]
+        path = os.path.join(dirname, f"out_matrix{gid}.npy")
+        np.save(path, out.float().cpu().numpy())
+        log(f"bench.py: wrote {path}: {rows} of {m} rows x {n}, float32")
 
 
 class TwinWorkload:
@@ -845,11 +890,14 @@ def main():
     wl.launch(0)
     if not cpu:
         torch.cuda.synchronize()
-    wl.sanity(args.dtype)
+    if args.full:
+        wl.sanity(args.dtype)
 
     # ---- timed regions: R repeats of exactly K steps, the median region is the result ---------
     my_times, launch_mode = time_steps(args, wl, dev, world)
     t_ms, per_rank_ms, maxima = median_region(my_times, dev, world)
+    if args.dump_outputs:
+        dump_outputs(wl, args.steps - 1, args.dump_outputs, sum(len(a) for a in all_mats))
 
     # ---- figures -------------------------------------------------------------------------------
     my_alg = wl.alg_bytes()
@@ -874,7 +922,7 @@ def main():
     # with no decode, timed the same way on the same rotation -- a reference point for
     # the access pattern, not a ceiling (tools/stream_probe.hip twin_mix) ----------------------
     twin = None
-    if not cpu and not args.no_ceiling and len(mats) == 1 and args.launch == "eager":
+    if args.full and not cpu and not args.no_ceiling and len(mats) == 1 and args.launch == "eager":
         twin = twin_measure(args, mats[0], dev, world, rank, my_alg, kt)
     if args.workload == "c5":
         metric = "dequantized elements/s (8 x 8192x8192 NF4->bf16, one matrix per GPU at N=8)"
@@ -893,6 +941,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": t_ms / args.steps,
         "higher_is_better": True,
         "scaling": scaling,
@@ -938,11 +987,11 @@ def main():
         "cpu_baseline": None,
         "c5": None,
     }
-    # ---- BASELINE configs[4] at this N (every N: the driver's scaling runs carry it) --------
-    if not args.no_c5 and args.workload != "c5":
+    # ---- BASELINE configs[4] at this N (--full, at every N) ------------------------------------
+    if args.full and not args.no_c5 and args.workload != "c5":
         res["c5"] = c5_section(args, rank, world, dev, dt, code, cpu)
-    # ---- CPU baseline: rank 0, after every timed region, at every N ---------------------------
-    if rank == 0 and not args.no_cpu_baseline:
+    # ---- CPU baseline (--full): rank 0, after every timed region, at every N -------------------
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         threads = max(1, min(16, int(os.environ.get("OMP_NUM_THREADS", "16") or 16), os.cpu_count() or 1))
         res["cpu_baseline"] = cpu_baseline(mats, args.cpu_seconds, code)
         if res["c5"] is not None:

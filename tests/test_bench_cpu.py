@@ -31,7 +31,7 @@ def _json(stdout):
 @pytest.mark.parametrize("n", [2, 3])
 def test_gpus_flag_spawns_ranks(n):
     p = _run(["--gpus", str(n), "--backend", "cpu", "--steps", "2", "--warmup", "1", "--m", "64", "--n", "128",
-              "--c5-shape", "64x128", "--cpu-seconds", "0.2"])
+              "--c5-shape", "64x128", "--cpu-seconds", "0.2", "--full"])
     assert p.returncode == 0, p.stderr[-3000:]
     d = _json(p.stdout)
     assert d["n_gpus"] == n and len(d["per_rank"]) == n
@@ -67,6 +67,66 @@ def test_gpus_flag_spawns_ranks(n):
         assert reg["in_sets"] >= 1 and reg["out_sets"] >= 1
         assert reg["read_footprint_bytes"] > 0 and reg["write_footprint_bytes"] > 0 and reg["weights_from"]
     assert c5["cpu_baseline"]["native"] > 0 and c5["cpu_baseline"]["value"] > 0
+
+
+@pytest.mark.timeout(120)
+def test_plain_run_is_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline alone (no c5 object, no CPU baseline),
+    K is the number of timed steps per region, and --dump-outputs writes the last step's
+    output as float32, equal to the oracle's dequantization of the seeded inputs."""
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(REPO, "oracle"))
+    import nf4_oracle as O
+    import workloads as W
+
+    out = tmp_path / "dump"
+    p = _run(["--gpus", "1", "--backend", "cpu", "--steps", "3", "--warmup", "1", "--m", "64", "--n", "128",
+              "--dump-outputs", str(out)])
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = _json(p.stdout)
+    assert d["full"] is False and d["c5"] is None and d["cpu_baseline"] is None
+    assert d["steps"] == 3 and d["repeats"]["steps_per_region"] == 3
+    assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(64 * 128 / (d["ms_per_step"] * 1e-3), rel=1e-6)
+    assert sorted(os.listdir(out)) == ["out_matrix0.npy"]
+    got = np.load(out / "out_matrix0.npy")
+    assert got.dtype == np.float32 and got.shape == (64, 128)
+    packed, a1, a2 = W.make_inputs(64, 128, 3409)
+    want = O.dequant_ref_np(packed, a1, a2, 64, 128, O.BF16)
+    assert np.array_equal(got.view(np.uint32), want.astype(np.uint32).reshape(64, 128) << 16)
+
+
+def test_dump_outputs_samples_rows_past_the_size_limit(tmp_path, monkeypatch):
+    """A matrix past its share of the limit is written as the same seeded, ascending
+    sample of whole rows in every run; the limit is shared by all ranks' matrices."""
+    import numpy as np
+    import torch
+    from types import SimpleNamespace
+
+    sys.path.insert(0, REPO)
+    import bench
+
+    m, n = 40, 16
+    # row r of matrix g holds r + 64 g in every column (exact in bf16)
+    outs = [(torch.arange(m, dtype=torch.float32)[:, None] + 64 * g).expand(m, n).to(torch.bfloat16) for g in range(2)]
+    wl = SimpleNamespace(mats=[(3, m, n), (5, m, n)], outs=[None, outs], Pout=2)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 10 * n * 4)  # 4 matrices in all: 10 rows each
+    dumps = []
+    for name in ("a", "b"):
+        bench.dump_outputs(wl, 5, str(tmp_path / name), 4)  # step 5 wrote output set 5 % 2
+        dumps.append([np.load(tmp_path / name / f"out_matrix{g}.npy") for g in (3, 5)])
+    for g, (a, b) in enumerate(zip(*dumps)):
+        assert a.dtype == np.float32 and a.shape == (10, n) and np.array_equal(a, b)
+        assert (a == a[:, :1]).all()  # whole rows
+        rows = (a[:, 0] - 64 * g).tolist()
+        assert rows == sorted(set(rows)) and 0 <= rows[0] and rows[-1] < m  # distinct rows of g, ascending
+
+
+def test_dump_outputs_limit_is_under_64_mb():
+    sys.path.insert(0, REPO)
+    import bench
+
+    assert bench.DUMP_MAX_BYTES + 8 * 128 <= 64_000_000  # 8 c5 files' .npy headers beside the data
 
 
 @pytest.mark.timeout(300)

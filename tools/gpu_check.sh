@@ -16,5 +16,5 @@ step() {  # step <name> <seconds> <cmd...>
 }
 [ "${SKIP_TESTS:-0}" = 1 ] || step pytest_gpu 900 python -u -m pytest tests -m gpu -q --maxfail=20 --timeout 120 --timeout-method thread
 [ "${SKIP_SMOKE:-0}" = 1 ] || step smoke 300 python __graft_entry__.py smoke
-[ "${SKIP_BENCH:-0}" = 1 ] || step bench 600 python bench.py ${BENCH_ARGS:-}
+[ "${SKIP_BENCH:-0}" = 1 ] || step bench 600 python bench.py --full ${BENCH_ARGS:-}
 exit 0

@@ -10,7 +10,7 @@ M=gpurun_out/meas
 mkdir -p $M
 # tool libraries are built here, not on the box (make -C tools)
 test -f tools/_build/libpmccalib.so || { echo 'tools/_build/libpmccalib.so missing: run make -C tools first' >&2; exit 2; }
-timeout -k 10 300 python -u bench.py > $M/bench.log 2> $M/bench.err && timeout -k 10 120 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline > $M/bench_k20.log 2>> $M/bench.err
+timeout -k 10 300 python -u bench.py --full > $M/bench.log 2> $M/bench.err && timeout -k 10 120 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $M/bench_k20.log 2>> $M/bench.err
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $M/rocprof -o bench -- \
     python -u bench.py --steps 200 --no-cpu-baseline > $M/bench_rocprof.log 2>&1
 python tools/rocprof_summary.py $M/rocprof nf4_flat_kernel $M/rocprof_bench_summary.json \

@@ -31,12 +31,12 @@ for stage in "$@"; do
     smoke)
         timeout -k 10 300 $PY __graft_entry__.py smoke > "$O/smoke.log" 2>&1; cat "$O/smoke.log" ;;
     bench)
-        timeout -k 10 300 $PY bench.py > "$O/bench.json" 2> "$O/bench.err"; cat "$O/bench.json" ;;
+        timeout -k 10 300 $PY bench.py --full > "$O/bench.json" 2> "$O/bench.err"; cat "$O/bench.json" ;;
     bench20)
-        timeout -k 10 200 $PY bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$O/bench_k20.json" 2>> "$O/bench.err"
+        timeout -k 10 200 $PY bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$O/bench_k20.json" 2>> "$O/bench.err"
         cat "$O/bench_k20.json" ;;
     multirank)  # N ranks on the one GPU of a lease (gloo; the driver's 8-GPU node runs RCCL)
-        timeout -k 10 400 $PY bench.py --gpus 2 --dist-backend gloo --steps 20 --warmup 5 > "$O/bench_g2_gloo.json" 2> "$O/bench_g2.err"
+        timeout -k 10 400 $PY bench.py --full --gpus 2 --dist-backend gloo --steps 20 --warmup 5 > "$O/bench_g2_gloo.json" 2> "$O/bench_g2.err"
         cat "$O/bench_g2_gloo.json" ;;
     c5probe)
         timeout -k 10 400 $PY tools/c5_probe.py > "$O/c5_probe.jsonl" 2> "$O/c5_probe.err"; cat "$O/c5_probe.jsonl" ;;
@@ -44,8 +44,8 @@ for stage in "$@"; do
         timeout -k 10 300 $PY tools/value_sensitivity.py > "$O/value_sensitivity.jsonl" 2> "$O/vs.err"
         cat "$O/value_sensitivity.jsonl" ;;
     c5bench)
-        timeout -k 10 200 $PY bench.py --m 8192 --n 8192 --steps 64 --no-cpu-baseline > "$O/bench_8192.json" 2> "$O/bench_8192.err"
-        timeout -k 10 200 $PY bench.py --workload c5 --steps 20 --no-cpu-baseline > "$O/bench_c5.json" 2> "$O/bench_c5.err"
+        timeout -k 10 200 $PY bench.py --full --m 8192 --n 8192 --steps 64 --no-cpu-baseline > "$O/bench_8192.json" 2> "$O/bench_8192.err"
+        timeout -k 10 200 $PY bench.py --full --workload c5 --steps 20 --no-cpu-baseline > "$O/bench_c5.json" 2> "$O/bench_c5.err"
         timeout -k 10 600 $PY tools/bench_configs.py --configs c5 > "$O/configs_c5.jsonl" 2> "$O/configs_c5.err"
         cat "$O/bench_8192.json" "$O/bench_c5.json" "$O/configs_c5.jsonl" ;;
     c5knobs)  # launch-shape variants at 8192^2 (eager, per-set absmax): KNOBS="label:args;label:args"
