@@ -124,6 +124,51 @@ int nf4_dequant_bnb_single(const uint8_t* packed, const float* absmax, int64_t n
                            void* out, int32_t out_dtype, int64_t numel,
                            int32_t blocksize, void* hip_stream);
 
+/* The producer side: quantize a flat stream of `numel` float elements (`in_dtype`:
+ * NF4DQ_F16 / NF4DQ_BF16 / NF4DQ_F32 name the INPUT type here) into the layout the
+ * nf4_dequant_bnb* entries read.  The specification is the package's Python quantizer
+ * (bnb_layout.quantize_nf4), bit for bit:
+ *   absmax[b] = max |x| over block b in fp32 (elements past numel read as 0)
+ *   q         = x / (absmax[b] > 0 ? absmax[b] : 1)        one IEEE fp32 division
+ *   code      = #{ j : (NF4[j] + NF4[j+1]) / 2 < q }       a tie goes to the lower code
+ *   packed[i] = code[2i] << 4 | code[2i+1]                 an odd numel is padded with a 0 (code 7)
+ * Writes packed uint8[ceil(numel/2)] and absmax fp32[ceil(numel/blocksize)], nothing else.
+ * blocksize: a power of two, 64..4096.  blocksize 64 with `w` 16-byte aligned and `packed`
+ * 4-byte aligned takes the streaming kernel (one pass over the weight); every other
+ * alignment (down to the element's own) and block size takes a slower general kernel.
+ * NF4DQ_ERR_ARG: null pointer, bad dtype, unsupported blocksize, negative numel, `w` not
+ * aligned to its element or `absmax` not to 4 bytes.  numel == 0: NF4DQ_OK, nothing launched. */
+int nf4_quant_bnb(const void* w, int32_t in_dtype, int64_t numel, int32_t blocksize,
+                  void* packed, void* absmax, void* hip_stream);
+
+/* compress_statistics=True: the fp32 absmax goes to the workspace and is quantized in turn
+ * with the 256-entry code book `code2` (device pointer, ascending; bitsandbytes' dynamic map):
+ *   offset      = fp32( (sum of absmax, accumulated in fp64 in a fixed order) / nblk )
+ *   v[i]        = absmax[i] - offset                       fp32; elements past nblk read as 0
+ *   absmax2[g]  = max(max |v| over 256-block g, FLT_MIN)
+ *   absmax_q[i] = #{ j : (code2[j] + code2[j+1]) / 2 < v[i] / absmax2[i / 256] }
+ * Writes packed, absmax_q uint8[nblk], absmax2 fp32[ceil(nblk/256)], offset fp32[1] (on the
+ * device) and the workspace.  Three launches on `hip_stream`, no host synchronisation, no
+ * allocation, no float atomics (two runs give the same bits); capturable in a graph.
+ * `offset` is the correctly rounded fp64 mean; the Python quantizer's fp32 reduction may
+ * differ from it in the last bit, and absmax_q / absmax2 follow from the offset used.
+ * blocksize2 must be 256.  `workspace`: 8-byte aligned, nf4_quant_workspace_bytes(numel,
+ * blocksize) bytes, no initial contents required; a smaller one is NF4DQ_ERR_ARG. */
+size_t nf4_quant_workspace_bytes(int64_t numel, int32_t blocksize);
+int nf4_quant_bnb_nested(const void* w, int32_t in_dtype, int64_t numel, int32_t blocksize,
+                         const float* code2, int32_t blocksize2,
+                         void* packed, void* absmax_q, void* absmax2, void* offset,
+                         void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* Host forms: HOST pointers, synchronous, `threads` workers over the blocks (<= 0 = all
+ * hardware threads), no workspace; the same results bit for bit, the same error codes. */
+int nf4_quant_bnb_cpu(const void* w, int32_t in_dtype, int64_t numel, int32_t blocksize,
+                      void* packed, void* absmax, int32_t threads);
+int nf4_quant_bnb_nested_cpu(const void* w, int32_t in_dtype, int64_t numel, int32_t blocksize,
+                             const float* code2, int32_t blocksize2,
+                             void* packed, void* absmax_q, void* absmax2, void* offset,
+                             int32_t threads);
+
 /* Launch tuning (bench/tuning only; the entry points above use the default
  * {4, 0, 1, 0}).  tile_dwords must be 4 and nontemporal 1 (the tile shape and
  * the sc1+nt output stores every entry point uses; the other shapes and store

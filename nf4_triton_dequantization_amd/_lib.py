@@ -106,6 +106,11 @@ SIGNATURES = {
     "nf4_dequant_bnb_single": (ctypes.c_int, [_P, _P, _I64, _P, _I32, _I64, _I32, _P]),
     "nf4_dequant_ref_cfg": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I32, _I64, _I64,
                                            ctypes.POINTER(LaunchCfg), _P]),
+    "nf4_quant_workspace_bytes": (ctypes.c_size_t, [_I64, _I32]),
+    "nf4_quant_bnb": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _P, _P]),
+    "nf4_quant_bnb_nested": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _I32, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "nf4_quant_bnb_cpu": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _P, _I32]),
+    "nf4_quant_bnb_nested_cpu": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _I32, _P, _P, _P, _P, _I32]),
     "nf4_gemm_workspace_bytes": (ctypes.c_size_t, [_I64, _I64, _I64]),
     "nf4_gemm_ref": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I32, _I64, _I64, _P, ctypes.c_size_t,
                                     _P]),

@@ -159,6 +159,9 @@ class Params4bit(nn.Parameter):
         return out
 
 
+_FROM_SOURCE = object()  # Linear4bit.from_float(bias=...): take the source module's bias
+
+
 class Linear4bit(nn.Module):
     """Minimal ``bitsandbytes.nn.Linear4bit`` stand-in (NF4, optional nested absmax).
 
@@ -186,6 +189,42 @@ class Linear4bit(nn.Module):
         qs.shape = torch.Size((output_features, input_features))
         self.weight = Params4bit(packed, qs)
         self.bias = None if not bias else nn.Parameter(torch.zeros(output_features, device=device))
+
+    @classmethod
+    def from_float(cls, linear_or_weight, compute_dtype=None, compress_statistics: bool = True, bias=_FROM_SOURCE,
+                   blocksize: int = 64):
+        """Build the module from an ``nn.Linear`` or an ``[out, in]`` float weight through the
+        HIP quantizer (``quantize.nf4_quantize``), on the weight's device: no kaiming init, no
+        torch-op quantization.  ``bias``: by default an ``nn.Linear``'s own bias is carried over
+        (a bare weight has none); ``None`` / ``False`` drops it, a tensor replaces it.
+        ``quant_state.dtype`` is ``compute_dtype`` if given, else the weight's dtype."""
+        from .quantize import nf4_quantize
+
+        if isinstance(linear_or_weight, nn.Module):
+            weight = linear_or_weight.weight
+            if bias is _FROM_SOURCE:
+                bias = getattr(linear_or_weight, "bias", None)
+        else:
+            weight = linear_or_weight
+            if bias is _FROM_SOURCE:
+                bias = None
+        if weight.dim() != 2:
+            raise ValueError(f"Linear4bit.from_float: expected an [out_features, in_features] weight, got "
+                             f"{tuple(weight.shape)}")
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self.out_features, self.in_features = int(weight.shape[0]), int(weight.shape[1])
+        self.compute_dtype = compute_dtype
+        packed, qs = nf4_quantize(weight, blocksize=blocksize, compress_statistics=compress_statistics)
+        if compute_dtype is not None:
+            qs.dtype = compute_dtype
+        qs.shape = torch.Size((self.out_features, self.in_features))
+        self.weight = Params4bit(packed, qs)
+        if bias is None or bias is False:
+            self.bias = None
+        else:
+            self.bias = nn.Parameter(bias.detach().clone().to(weight.device), requires_grad=bias.requires_grad)
+        return self
 
     def _apply(self, fn, recurse=True):
         super()._apply(fn, recurse)

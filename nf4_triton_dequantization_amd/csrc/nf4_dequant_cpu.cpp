@@ -20,6 +20,7 @@
 // over `threads` std::thread workers (no OpenMP runtime: the library is loaded
 // into processes that already carry torch's).  A CPU without AVX2 takes the
 // portable scalar table loop (same tables, same results).
+#include <float.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -30,6 +31,7 @@
 #include <immintrin.h>
 
 #include "../../include/nf4_dequant.h"
+#include "nf4_quant_plan.h"
 
 namespace {
 
@@ -253,6 +255,172 @@ int nf4_dequant_single_cpu(const uint8_t* packed, int64_t packed_len, const floa
     J.n = n;
     J.bpr = bpr;
     return run<kSingle>(J, out_dtype, threads);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Host forms of the NF4 quantizer (nf4_quant.hip): the same arithmetic -- fp32 absmax,
+// one IEEE division per element, count of the midpoints below the quotient, fp64 absmax
+// sum in the order of nf4_quant_plan.h -- so the same bits.  Blocks are split over threads.
+// ---------------------------------------------------------------------------
+namespace {
+
+inline float quant_elem(const void* w, int32_t dt, int64_t i) {
+    if (dt == NF4DQ_F32) return reinterpret_cast<const float*>(w)[i];
+    const uint16_t h = reinterpret_cast<const uint16_t*>(w)[i];
+    if (dt == NF4DQ_BF16) {
+        const uint32_t u = (uint32_t)h << 16;
+        float f;
+        memcpy(&f, &u, 4);
+        return f;
+    }
+    _Float16 f;
+    memcpy(&f, &h, 2);
+    return (float)f;
+}
+
+inline float abs_f(float x) {
+    uint32_t u;
+    memcpy(&u, &x, 4);
+    u &= 0x7fffffffu;
+    memcpy(&x, &u, 4);
+    return x;
+}
+
+struct QuantMids {
+    float m[15];
+    QuantMids() {
+        for (int j = 0; j < 15; ++j) m[j] = (code_f(j) + code_f(j + 1)) / 2.0f;
+    }
+};
+
+inline uint32_t quant_code(float q, const QuantMids& M) {
+    uint32_t c = 0;
+    for (int j = 0; j < 15; ++j) c += M.m[j] < q ? 1u : 0u;
+    return c;
+}
+
+void quant_blocks(const void* w, int32_t dt, int64_t numel, int32_t bs, uint8_t* packed, float* absmax, int64_t b0,
+                  int64_t b1) {
+    static const QuantMids M;
+    for (int64_t b = b0; b < b1; ++b) {
+        const int64_t e0 = b * bs, e1 = std::min<int64_t>(numel, e0 + bs);
+        float amax = 0.0f;
+        for (int64_t i = e0; i < e1; ++i) {
+            const float a = abs_f(quant_elem(w, dt, i));
+            amax = a > amax ? a : amax;
+        }
+        absmax[b] = amax;
+        const float safe = amax > 0.0f ? amax : 1.0f;
+        for (int64_t i = e0; i < e1; i += 2) {
+            const uint32_t hi = quant_code(quant_elem(w, dt, i) / safe, M);
+            const uint32_t lo = i + 1 < numel ? quant_code(quant_elem(w, dt, i + 1) / safe, M) : 7u;  // pad 0 -> code 7
+            packed[i >> 1] = (uint8_t)(hi << 4 | lo);
+        }
+    }
+}
+
+// `count` items [0, count) split into contiguous ranges over up to `threads` workers
+template <class F>
+void split_ranges(int64_t count, int64_t min_per, int32_t threads, F&& fn) {
+    int64_t t = threads > 0 ? threads : (int64_t)std::max(1u, std::thread::hardware_concurrency());
+    t = std::max<int64_t>(1, std::min<int64_t>(t, (count + min_per - 1) / min_per));
+    const int64_t per = (count + t - 1) / t;
+    std::vector<std::thread> pool;
+    for (int64_t i = 1; i < t; ++i) {
+        const int64_t r0 = i * per, r1 = std::min(count, r0 + per);
+        if (r0 >= r1) break;
+        pool.emplace_back([&fn, r0, r1] { fn(r0, r1); });
+    }
+    fn(0, std::min(count, per));
+    for (auto& th : pool) th.join();
+}
+
+// sum_ordered of nf4_quant_plan.h
+template <class T>
+double sum_ordered(const T* v, int64_t n) {
+    double slot[nf4q::kBlock2];
+    for (int t = 0; t < nf4q::kBlock2; ++t) {
+        double acc = 0.0;
+        for (int64_t i = t; i < n; i += nf4q::kBlock2) acc += (double)v[i];
+        slot[t] = acc;
+    }
+    for (int s = nf4q::kBlock2 / 2; s; s >>= 1)
+        for (int t = 0; t < s; ++t) slot[t] += slot[t + s];
+    return slot[0];
+}
+
+int quant_check(const void* w, int32_t dt, int64_t numel, int32_t bs, const void* packed) {
+    if (dt != NF4DQ_F16 && dt != NF4DQ_BF16 && dt != NF4DQ_F32) return NF4DQ_ERR_ARG;
+    if (numel < 0 || !nf4q::valid_blocksize(bs)) return NF4DQ_ERR_ARG;
+    if (numel == 0) return NF4DQ_OK;
+    if (!w || !packed) return NF4DQ_ERR_ARG;
+    return NF4DQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nf4_quant_bnb_cpu(const void* w, int32_t in_dtype, int64_t numel, int32_t blocksize, void* packed, void* absmax,
+                      int32_t threads) {
+    const int rc = quant_check(w, in_dtype, numel, blocksize, packed);
+    if (rc || numel == 0) return rc;
+    if (!absmax) return NF4DQ_ERR_ARG;
+    const int64_t nblk = (numel + blocksize - 1) / blocksize;
+    uint8_t* p = reinterpret_cast<uint8_t*>(packed);
+    float* am = reinterpret_cast<float*>(absmax);
+    // at least 64 Ki elements per worker
+    split_ranges(nblk, std::max<int64_t>(1, 65536 / blocksize), threads, [=](int64_t b0, int64_t b1) {
+        quant_blocks(w, in_dtype, numel, blocksize, p, am, b0, b1);
+    });
+    return NF4DQ_OK;
+}
+
+int nf4_quant_bnb_nested_cpu(const void* w, int32_t in_dtype, int64_t numel, int32_t blocksize, const float* code2,
+                             int32_t blocksize2, void* packed, void* absmax_q, void* absmax2, void* offset,
+                             int32_t threads) {
+    int rc = quant_check(w, in_dtype, numel, blocksize, packed);
+    if (rc) return rc;
+    if (blocksize2 != nf4q::kBlock2) return NF4DQ_ERR_ARG;
+    if (numel == 0) return NF4DQ_OK;
+    if (!code2 || !absmax_q || !absmax2 || !offset) return NF4DQ_ERR_ARG;
+    const int64_t nblk = (numel + blocksize - 1) / blocksize;
+    std::vector<float> am((size_t)nblk);
+    rc = nf4_quant_bnb_cpu(w, in_dtype, numel, blocksize, packed, am.data(), threads);
+    if (rc) return rc;
+    const nf4q::SumPlan sp = nf4q::sum_plan(nblk);
+    std::vector<double> parts((size_t)sp.parts);
+    for (int32_t p = 0; p < sp.parts; ++p) {
+        const int64_t b0 = (int64_t)p * sp.chunk;
+        parts[(size_t)p] = sum_ordered(am.data() + b0, std::min(nblk - b0, sp.chunk));
+    }
+    const float off = (float)(sum_ordered(parts.data(), sp.parts) / (double)nblk);
+    *reinterpret_cast<float*>(offset) = off;
+    float mids[255];
+    for (int j = 0; j < 255; ++j) mids[j] = (code2[j] + code2[j + 1]) / 2.0f;
+    uint8_t* aq = reinterpret_cast<uint8_t*>(absmax_q);
+    float* a2 = reinterpret_cast<float*>(absmax2);
+    const int64_t n2 = (nblk + nf4q::kBlock2 - 1) / nf4q::kBlock2;
+    const float* amp = am.data();
+    split_ranges(n2, 64, threads, [=, &mids](int64_t g0, int64_t g1) {
+        for (int64_t g = g0; g < g1; ++g) {
+            const int64_t i0 = g * nf4q::kBlock2, i1 = std::min(nblk, i0 + nf4q::kBlock2);
+            float m = 0.0f;
+            for (int64_t i = i0; i < i1; ++i) {
+                const float a = abs_f(amp[i] - off);
+                m = a > m ? a : m;
+            }
+            m = m > FLT_MIN ? m : FLT_MIN;
+            a2[g] = m;
+            for (int64_t i = i0; i < i1; ++i) {
+                const float q = (amp[i] - off) / m;
+                aq[i] = (uint8_t)(std::lower_bound(mids, mids + 255, q) - mids);
+            }
+        }
+    });
+    return NF4DQ_OK;
 }
 
 }  // extern "C"
