@@ -8,44 +8,22 @@ plus one final rounding to the output dtype,
 where sub = half the output dtype's subnormal spacing (2^-25 fp16, 2^-134 bf16): an
 output in the subnormal range rounds to an absolute, not a relative, grid (a drawn
 fp16 case with y = 6.7e-7 is off by 9.7e-9 even when rounded from the exact sum).
+The oracle's helpers and the comparison live in tests/_gemm_cases.py: an element passes
+only if ``abs(y - ref) <= tol`` is true, so a NaN or inf output fails.
 """
 import numpy as np
 import pytest
 import torch
 
 import nf4_oracle as O
+from _gemm_cases import GEMV_FORMS, check_close_t
+from _gemm_cases import bits_to_f64 as _bits_to_f64
+from _gemm_cases import check_gemm as _check  # fails on NaN / inf outputs too (abs(got - ref) <= tol must hold)
+from _gemm_cases import tol as _tol
+from _gemm_cases import x_bits as _x_bits
 from _helpers import make_module
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits_to_f64(bits, dt):
-    if dt == "f16":
-        return bits.view(np.float16).astype(np.float64)
-    return (bits.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
-
-
-def _tol(ref, mag, dt):
-    p, sub = (8, 2.0 ** -134) if dt == "bf16" else (10, 2.0 ** -25)
-    return 2.0 ** -p * np.abs(ref) + 2.0 ** -20 * mag + sub
-
-
-def _check(y, x_bits, w_bits, dt):
-    xf = _bits_to_f64(x_bits, dt)
-    wf = _bits_to_f64(w_bits, dt)
-    ref = xf @ wf.T
-    mag = np.abs(xf) @ np.abs(wf).T
-    tol = _tol(ref, mag, dt)
-    yb = y.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
-    got = _bits_to_f64(yb, dt).reshape(ref.shape)
-    bad = np.abs(got - ref) > tol
-    assert not bad.any(), f"{bad.sum()} of {bad.size} outside tolerance; worst {np.abs(got - ref).max():.3g}"
-
-
-def _x_bits(M, K, dt, seed):
-    x = O.normal_f32(seed, M * K, stream=9).reshape(M, K)
-    t = torch.from_numpy(x).to(torch.float16 if dt == "f16" else torch.bfloat16)
-    return t, t.view(torch.int16).numpy().view(np.uint16)
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
@@ -263,8 +241,7 @@ def test_every_decomposition_agrees_with_oracle(coracle, gpu, dt, M, N, K):
                         if rc == _lib.ERR_ARG:
                             continue
                         assert rc == 0, (kernel, waves, depth, strips, ks, rc)
-                        bad = ((y.double() - ref).abs() > tol) | torch.isnan(y)
-                        assert not bool(bad.any()), (kernel, waves, depth, strips, ks, int(bad.sum()))
+                        check_close_t(y, ref, tol, (kernel, waves, depth, strips, ks))
                         ran += 1
     assert ran >= 12
 
@@ -330,8 +307,7 @@ def test_gemv_every_decomposition(coracle, gpu, dt, N, K):
                 y.fill_(float("nan"))
                 rc = _gemm_cfg_call(L, _lib, x, t, y, code, N, K, cfg)
                 assert rc == 0, (waves, rows, wgs, rc)
-                bad = ((y.double() - ref).abs() > tol) | torch.isnan(y)
-                assert not bool(bad.any()), (waves, rows, wgs, int(bad.sum()))
+                check_close_t(y, ref, tol, (waves, rows, wgs))
 
 
 def test_invalid_decompositions_rejected(gpu):
@@ -972,3 +948,173 @@ def test_release_gemm_workspaces_empties_the_cache(gpu):
     y1 = nf4_linear(xt.to(gpu), mod)
     torch.cuda.synchronize()
     assert kernel._GEMM_WS and torch.equal(y0.view(torch.int16), y1.view(torch.int16))
+
+
+# ---- the decode GEMV over several weights (its multi-weight walk) and wrapping absmax --------
+def _group_on_device(coracle, gpu, dt, K, inputs):
+    """inputs: [(N, packed, a1, a2)] -> (mats, ys, oracle weights, tensors kept alive);
+    every y pre-filled with NaN."""
+    from nf4_triton_dequantization_amd import _lib
+
+    tdt = torch.bfloat16 if dt == "bf16" else torch.float16
+    mats = (_lib.GemmMat * len(inputs))()
+    ys, Ws, keep = [], [], []
+    for i, (N, packed, a1, a2) in enumerate(inputs):
+        Ws.append(coracle.dequant_ref(packed, a1, a2, N, K, O.BF16 if dt == "bf16" else O.F16))
+        t = [torch.from_numpy(v).to(gpu) for v in (packed, a1, a2)]
+        keep.append(t)
+        y = torch.full((1, N), float("nan"), dtype=tdt, device=gpu)
+        ys.append(y)
+        mats[i] = _lib.GemmMat(t[0].data_ptr(), t[0].numel(), t[1].data_ptr(), t[1].numel(), t[2].data_ptr(),
+                               t[2].numel(), y.data_ptr(), N)
+    return mats, ys, Ws, keep
+
+
+def _grouped_m1(L, _lib, x, K, mats, ys, dt, cfg):
+    """One grouped M = 1 launch (cfg None: the library's choice) into NaN-filled outputs."""
+    import ctypes
+
+    for y in ys:
+        y.fill_(float("nan"))
+    wsz = L.nf4_gemm_grouped_workspace_bytes(1, K, mats, len(ys), ctypes.byref(cfg) if cfg is not None else None)
+    ws = torch.zeros(max(wsz, 16), dtype=torch.uint8, device=x.device)
+    rc = L.nf4_gemm_ref_grouped(x.data_ptr(), 1, K, mats, len(ys), _lib.BF16 if dt == "bf16" else _lib.F16,
+                                ws.data_ptr() if wsz else None, wsz, ctypes.byref(cfg) if cfg is not None else None,
+                                torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return rc
+
+
+def _m1_oracles(xb, Ws, dt, gpu):
+    out = []
+    xf = _bits_to_f64(xb, dt)
+    for W in Ws:
+        wf = _bits_to_f64(W, dt)
+        ref = xf @ wf.T
+        out.append((torch.from_numpy(ref).to(gpu), torch.from_numpy(_tol(ref, np.abs(xf) @ np.abs(wf).T, dt)).to(gpu)))
+    return out
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("K,Ns", [(2048, (2048, 512, 512)), (4096, (1024, 1024, 2048)), (2048, (64, 64))])
+def test_grouped_gemv_default_path(coracle, gpu, dt, K, Ns):
+    """Grouped launches the library gives to the decode GEMV (M = 1, <= 4096 columns in
+    all, K % 2048 == 0): its walk over several weights (first-weight scan, weight switches
+    between row groups, per-weight descriptors and outputs), through nf4_linear_grouped
+    and through the C ABI into NaN-filled outputs."""
+    from nf4_triton_dequantization_amd import _lib, nf4_linear_grouped
+
+    assert sum(Ns) <= 4096 and K % 2048 == 0
+    inputs = [(N,) + tuple(O.make_inputs(N, K, seed=3 * N + K + 17 * i, a2_kind="normal")) for i, N in enumerate(Ns)]
+    mats, ys, Ws, _keep = _group_on_device(coracle, gpu, dt, K, inputs)
+    xt, xb = _x_bits(1, K, dt, seed=K + len(Ns))
+    x = xt.to(gpu)
+    oracles = _m1_oracles(xb, Ws, dt, gpu)
+    mods = [make_module(p, a1, a2, N, K, dt, gpu) for (N, p, a1, a2) in inputs]
+    got = nf4_linear_grouped(x, mods)
+    assert len(got) == len(Ns)
+    for i, (y, (ref, tol)) in enumerate(zip(got, oracles)):
+        check_close_t(y, ref, tol, f"nf4_linear_grouped weight {i} of {Ns}")
+    rc = _grouped_m1(_lib.lib(), _lib, x, K, mats, ys, dt, None)
+    assert rc == 0, _lib.strerror(rc)
+    for i, (y, (ref, tol)) in enumerate(zip(ys, oracles)):
+        check_close_t(y, ref, tol, f"C ABI weight {i} of {Ns}")
+
+
+# (waves, rows per group) forms by the widths at which, on 256 CUs, a wave walks more than
+# one row group and crosses a weight boundary
+_GEMV_WALKS = [((2048, 512, 512), [(8, 1)]),
+               ((4096, 1024, 1024), [(16, 1), (8, 2)]),
+               ((8192, 2048, 2048), [(8, 4), (16, 2)]),
+               ((12288, 4096, 2048), [(16, 4)])]
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("Ns,forms", _GEMV_WALKS)
+def test_grouped_gemv_waves_walk_across_weights(coracle, gpu, dt, Ns, forms):
+    """Explicit GEMV configurations over three weights with more row groups than the grid
+    has waves: every wave walks on to a second row group (next_unit / advance_p), and for
+    many that group lies in another weight (new descriptors, row_begin, row bases, y)."""
+    from nf4_triton_dequantization_amd import _lib
+
+    L = _lib.lib()
+    K = 2048
+    cus = torch.cuda.get_device_properties(gpu).multi_processor_count
+    inputs = [(N,) + tuple(O.make_inputs(N, K, seed=5 * N + 23 * i, a2_kind="normal")) for i, N in enumerate(Ns)]
+    mats, ys, Ws, _keep = _group_on_device(coracle, gpu, dt, K, inputs)
+    xt, xb = _x_bits(1, K, dt, seed=sum(Ns) % 1000)
+    x = xt.to(gpu)
+    oracles = _m1_oracles(xb, Ws, dt, gpu)
+    for waves, rows in forms:
+        for wgs in (0, 1):  # workgroups per CU: 0 means 1
+            # not vacuous on a part with more CUs: more row groups than waves in the grid
+            assert sum(Ns) / rows > cus * waves * max(wgs, 1), (sum(Ns), rows, cus, waves, wgs)
+            cfg = _lib.GemmCfg(_lib.GEMM_GEMV, waves, rows, 1, wgs)
+            rc = _grouped_m1(L, _lib, x, K, mats, ys, dt, cfg)
+            assert rc == 0, (waves, rows, wgs, _lib.strerror(rc))
+            for i, (y, (ref, tol)) in enumerate(zip(ys, oracles)):
+                check_close_t(y, ref, tol, f"GEMV ({waves}, {rows}, {wgs}) weight {i} of {Ns}")
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+def test_grouped_gemv_every_form_narrow_weights(coracle, gpu, dt):
+    """Ns = (64, 192, 64): 320 rows, so the last workgroup has waves without a row group
+    and, at 2 and 4 rows per group, weight boundaries fall after 32 / 16 row groups."""
+    from nf4_triton_dequantization_amd import _lib
+
+    L = _lib.lib()
+    K, Ns = 2048, (64, 192, 64)
+    inputs = [(N,) + tuple(O.make_inputs(N, K, seed=7 * N + 29 * i, a2_kind="normal")) for i, N in enumerate(Ns)]
+    mats, ys, Ws, _keep = _group_on_device(coracle, gpu, dt, K, inputs)
+    xt, xb = _x_bits(1, K, dt, seed=320)
+    x = xt.to(gpu)
+    oracles = _m1_oracles(xb, Ws, dt, gpu)
+    for waves, rows in GEMV_FORMS:
+        for wgs in (0, 1, 2):
+            cfg = _lib.GemmCfg(_lib.GEMM_GEMV, waves, rows, 1, wgs)
+            rc = _grouped_m1(L, _lib, x, K, mats, ys, dt, cfg)
+            assert rc == 0, (waves, rows, wgs, _lib.strerror(rc))
+            for i, (y, (ref, tol)) in enumerate(zip(ys, oracles)):
+                check_close_t(y, ref, tol, f"GEMV ({waves}, {rows}, {wgs}) weight {i}")
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("K", [2048, 4096])
+def test_gemv_absmax_wrapping_at_row_boundaries(coracle, gpu, dt, K):
+    """absmax of 5 rows' worth and nested absmax of 3 rows' worth (nb = 5 K/64, n2 = 3
+    ceil(K/256)): the reference's repeat wraps between rows, never inside one, which the
+    GEMV accepts and indexes with a per-row modulo.  An explicit GEMV configuration
+    returning 0 proves the GEMV ran (it answers ERR_ARG where it cannot; no fallback)."""
+    from nf4_triton_dequantization_amd import _lib, nf4_linear, nf4_linear_grouped
+
+    L = _lib.lib()
+    bpr = K // 64
+    groups = -(-bpr // 4)
+    Ns = (64, 192, 64)
+    inputs = [(N,) + tuple(O.golden_case_inputs(N, K, 60 + i, {"nb": 5 * bpr, "n2": 3 * groups,
+                                                                "a2_kind": "normal"})[:3])
+              for i, N in enumerate(Ns)]
+    for (N, _p, a1, a2) in inputs:
+        assert a1.size == 5 * bpr < N * bpr and a2.size == 3 * groups < N * groups
+    mats, ys, Ws, keep = _group_on_device(coracle, gpu, dt, K, inputs)
+    xt, xb = _x_bits(1, K, dt, seed=K + 5)
+    x = xt.to(gpu)
+    oracles = _m1_oracles(xb, Ws, dt, gpu)
+    code = _lib.BF16 if dt == "bf16" else _lib.F16
+    for waves, rows in GEMV_FORMS:
+        cfg = _lib.GemmCfg(_lib.GEMM_GEMV, waves, rows, 1, 0)
+        rc = _grouped_m1(L, _lib, x, K, mats, ys, dt, cfg)
+        assert rc == 0, (waves, rows, _lib.strerror(rc))
+        for i, (y, (ref, tol)) in enumerate(zip(ys, oracles)):
+            check_close_t(y, ref, tol, f"grouped GEMV ({waves}, {rows}) weight {i}")
+        # single weight: the 192-row one
+        y = ys[1]
+        y.fill_(float("nan"))
+        rc = _gemm_cfg_call(L, _lib, x, keep[1], y, code, Ns[1], K, cfg)
+        assert rc == 0, (waves, rows, _lib.strerror(rc))
+        check_close_t(y, oracles[1][0], oracles[1][1], f"single GEMV ({waves}, {rows})")
+    # and the library's own choice (the GEMV at these shapes)
+    mods = [make_module(p, a1, a2, N, K, dt, gpu) for (N, p, a1, a2) in inputs]
+    for i, (y, (ref, tol)) in enumerate(zip(nf4_linear_grouped(x, mods), oracles)):
+        check_close_t(y, ref, tol, f"nf4_linear_grouped weight {i}")
+    check_close_t(nf4_linear(x, mods[1]), oracles[1][0], oracles[1][1], "nf4_linear")

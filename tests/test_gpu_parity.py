@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import nf4_oracle as O
+from _gemm_cases import double_rounding_cases
 from _helpers import (DT_CODE, assert_bits_equal, big_samples, load_case, make_module, max_abs_diff, out_bits,
                       sha, torch_dtype)
 
@@ -241,27 +242,10 @@ def test_linear4bit_layout_and_forward(gpu):
 def _double_rounding_scales(dt, count=64, seed=1):
     """Scales s and codes c where RNE16(fp32(NF4[c]*s)) != RNE16(exact NF4[c]*s): the
     reference rounds twice (fp32 product, then 16-bit cast); a fused multiply-convert
-    would round once and differ exactly here."""
-    rng = np.random.default_rng(seed)
-    found_s, found_c = [], []
-    lut = O.NF4_LUT.astype(np.float64)
-    while len(found_s) < count:
-        s = (rng.random(1 << 20) * 2.0 + 0.01).astype(np.float32)
-        c = rng.integers(0, 16, 1 << 20)
-        exact = lut[c] * s.astype(np.float64)
-        f32 = exact.astype(np.float32)
-        if dt == "f16":
-            twice = f32.astype(np.float16).view(np.uint16)
-            once = exact.astype(np.float16).view(np.uint16)
-        else:
-            twice = O.f32_to_bf16_bits(f32)
-            u = exact.view(np.uint64)  # RNE of float64 to bf16 (8-bit mantissa)
-            once = ((u + np.uint64(0x7FFFFFFFFFFF) + ((u >> np.uint64(48)) & np.uint64(1))) >> np.uint64(48))
-            once = once.astype(np.uint16)
-        hit = np.nonzero(twice != once)[0]
-        found_s += s[hit].tolist()
-        found_c += c[hit].tolist()
-    return np.array(found_s[:count], np.float32), np.array(found_c[:count])
+    would round once and differ exactly here.  (From tests/_gemm_cases.py, whose bf16
+    rounding keeps 8 significant bits; tests/test_gemm_cases_cpu.py re-derives every
+    case with exact fractions.)"""
+    return double_rounding_cases(dt, count, seed)
 
 
 @pytest.mark.parametrize("dt", ["f16", "bf16"])

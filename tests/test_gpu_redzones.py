@@ -19,6 +19,7 @@ import pytest
 import torch
 
 import nf4_oracle as O
+from _gemm_cases import cfg_tuple, check_close, check_close_t, gemm_cfgs
 from _helpers import DT_CODE, assert_bits_equal, out_bits, torch_dtype
 
 pytestmark = pytest.mark.gpu
@@ -151,25 +152,6 @@ def test_bnb(coracle, gpu, bs):
         _inputs_intact([(gp, p), (ga1, a1), (gc, code2), (ga2, a2), (gam, am)])
 
 
-def _gemm_cfgs(K):
-    from nf4_triton_dequantization_amd import _lib
-
-    chunks = K // 128
-    for kernel in (_lib.GEMM_PERSIST, _lib.GEMM_STREAM, _lib.GEMM_K128):
-        for waves in (4, 8, 16):
-            for depth in (1, 2, 4):
-                for strips in (1, 2, 4):
-                    for ks in (1, 2, 3):
-                        yield _lib.GemmCfg(kernel, waves, depth, ks, strips)
-    for waves in (4, 8):
-        for kc in (2, 4, 8):
-            yield _lib.GemmCfg(_lib.GEMM_XS, waves, kc, -(-chunks // kc), 1)
-    for waves in (8, 16):
-        for depth in (2, 4):
-            for kpw in (1, 2, 4):
-                yield _lib.GemmCfg(_lib.GEMM_XR, waves, depth, -(-chunks // (waves * kpw)), kpw)
-
-
 def _gemm_ref(W_bits, x_bits):
     xf = (x_bits.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
     wf = (W_bits.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
@@ -191,8 +173,8 @@ def test_gemm_every_decomposition(coracle, gpu, M, N, K):
     ref, tol = _gemm_ref(W, xb)
     ref_t, tol_t = torch.from_numpy(ref).to(gpu), torch.from_numpy(tol).to(gpu)
     gp, ga1, ga2, gx = (Guarded.of(v, gpu) for v in (p, a1, a2, xb))
-    ran = 0
-    for cfg in _gemm_cfgs(K):
+    ran = gemv = 0
+    for cfg in gemm_cfgs(K, M):  # the shared list: the GEMV's forms too at the M = 1 shape
         wsz = L.nf4_gemm_workspace_bytes_cfg(M, N, K, ctypes.byref(cfg))
         ws = Guarded(wsz, gpu, fill=0)
         y = Guarded(M * N * 2, gpu, fill=0x5A)
@@ -201,7 +183,7 @@ def test_gemm_every_decomposition(coracle, gpu, M, N, K):
         torch.cuda.synchronize()
         if rc == _lib.ERR_ARG:
             continue
-        what = (cfg.kernel, cfg.waves, cfg.depth, cfg.ksplit, cfg.strips)
+        what = cfg_tuple(cfg)
         assert rc == 0, (what, _lib.strerror(rc))
         assert y.bands_intact(), f"write outside y, cfg {what}"
         assert ws.bands_intact(), f"write outside the workspace, cfg {what}"
@@ -211,11 +193,12 @@ def test_gemm_every_decomposition(coracle, gpu, M, N, K):
             # tickets back at 0 and every split-K slab entry read and cleared (empty) again
             assert int(ws.body()[:min(COUNTER_BYTES, wsz)].count_nonzero()) == 0, f"tickets not reset, cfg {what}"
             assert int(ws.body().count_nonzero()) == 0, f"slab entries not cleared, cfg {what}"
-        bad = (y.body(torch.bfloat16).view(M, N).double() - ref_t).abs() > tol_t
-        assert not bool(bad.any()), (what, int(bad.sum()))
+        check_close_t(y.body(torch.bfloat16).view(M, N), ref_t, tol_t, what)
         ran += 1
+        gemv += cfg.kernel == _lib.GEMM_GEMV
     _inputs_intact([(gp, p), (ga1, a1), (ga2, a2), (gx, xb)])
     assert ran >= 8, ran
+    assert gemv == (18 if M == 1 else 0), gemv  # K = 2048 at the M = 1 shape: every GEMV form runs
 
 
 def test_gemm_grouped(coracle, gpu):
@@ -249,6 +232,48 @@ def test_gemm_grouped(coracle, gpu):
         assert y.bands_intact(), f"write outside y of the {N}-column weight"
         ref, tol = _gemm_ref(coracle.dequant_ref(p, a1, a2, N, K, O.BF16), xb)
         got = y.body(torch.bfloat16).view(M, N).double().cpu().numpy()
-        assert not (np.abs(got - ref) > tol).any(), N
+        check_close(got, ref, tol, f"the {N}-column weight")
+        _inputs_intact([(gp, p), (ga1, a1), (ga2, a2)])
+    _inputs_intact([(gx, xb)])
+
+
+@pytest.mark.parametrize("cfg", [None, (8, 4)])
+def test_gemm_grouped_decode_gemv(coracle, gpu, cfg):
+    """A grouped M = 1 launch the decode GEMV takes (the library's choice, and 8 waves x 4
+    rows per group): K = 2048, Ns = (64, 192, 64).  The GEMV writes y with plain pointer
+    stores, one row group per wave at a time, from per-weight descriptors: every buffer
+    sits between guard bands and every y is exact-size."""
+    from nf4_triton_dequantization_amd import _lib
+
+    L = _lib.lib()
+    M, K = 1, 2048
+    Ns = (64, 192, 64)
+    c = _lib.GemmCfg(_lib.GEMM_GEMV, cfg[0], cfg[1], 1, 0) if cfg else None
+    cp = ctypes.byref(c) if c is not None else None
+    x = torch.from_numpy(O.normal_f32(11, M * K, stream=9).reshape(M, K)).to(torch.bfloat16)
+    xb = x.view(torch.int16).numpy().view(np.uint16)
+    gx = Guarded.of(xb, gpu)
+    mats = (_lib.GemmMat * len(Ns))()
+    keep = []
+    for i, N in enumerate(Ns):
+        p, a1, a2 = O.make_inputs(N, K, seed=400 + i, a2_kind="normal")
+        gp, ga1, ga2 = (Guarded.of(v, gpu) for v in (p, a1, a2))
+        y = Guarded(M * N * 2, gpu, fill=0x5A)
+        mats[i] = _lib.GemmMat(gp.ptr(), p.size, ga1.ptr(), a1.size, ga2.ptr(), a2.size, y.ptr(), N)
+        keep.append((N, gp, ga1, ga2, y, (p, a1, a2)))
+    wsz = L.nf4_gemm_grouped_workspace_bytes(M, K, mats, len(Ns), cp)
+    ws = Guarded(wsz, gpu, fill=0)
+    rc = L.nf4_gemm_ref_grouped(gx.ptr(), M, K, mats, len(Ns), _lib.BF16, ws.ptr() if wsz else None, wsz, cp,
+                                _stream())
+    torch.cuda.synchronize()
+    assert rc == 0, _lib.strerror(rc)
+    assert ws.bands_intact()
+    assert L.nf4_gemm_check_workspace(ws.ptr() if wsz else None, wsz, _stream()) == 0
+    if wsz:
+        assert int(ws.body().count_nonzero()) == 0
+    for N, gp, ga1, ga2, y, (p, a1, a2) in keep:
+        assert y.bands_intact(), f"write outside y of the {N}-column weight"
+        ref, tol = _gemm_ref(coracle.dequant_ref(p, a1, a2, N, K, O.BF16), xb)
+        check_close(y.body(torch.bfloat16).view(M, N).double().cpu().numpy(), ref, tol, f"the {N}-column weight")
         _inputs_intact([(gp, p), (ga1, a1), (ga2, a2)])
     _inputs_intact([(gx, xb)])

@@ -13,6 +13,7 @@ import torch
 from types import SimpleNamespace
 
 import nf4_oracle as O
+from _gemm_cases import check_close
 from _helpers import assert_bits_equal, out_bits
 
 pytestmark = pytest.mark.gpu
@@ -76,5 +77,4 @@ def test_linear_and_grouped_with_strided_inputs(coracle, gpu, M):
         for y, what in ((yg, "grouped"), (ys, "single")):
             got = y.float().cpu().double().numpy()
             assert got.shape == ref.shape
-            bad = np.abs(got - ref) > tol
-            assert not bad.any(), f"{what} {m}x{n} M={M}: {bad.sum()} outside tolerance"
+            check_close(got, ref, tol, f"{what} {m}x{n} M={M}")

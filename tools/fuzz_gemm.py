@@ -10,8 +10,11 @@ configuration of any of the six kernels through ``nf4_gemm_ref_cfg`` (invalid dr
 skipped; a split-K timeout flagged in the workspace counts as a failure). Each result is
 checked against a float64 product of the C oracle's dequantized weights with the GEMM
 suite's tolerance
-(tests/test_gpu_gemm.py: 2^-p |ref| + 2^-20 sum|x w|). One progress line per 100
-cases, then a summary.
+(tests/_gemm_cases.py: 2^-p |ref| + 2^-20 sum|x w|). Half of the ``--gemv-rate`` cases are
+grouped M = 1 launches (2-4 weights in multiples of 64 columns sharing x, some with absmax
+wrapping at row boundaries): up to 4096 columns in all through the library's choice, or up
+to 8192 with a drawn GEMV configuration; each output against its own oracle. One progress
+line per 100 cases, then a summary.
 """
 from __future__ import annotations
 
@@ -64,6 +67,67 @@ def random_cfg(rng, M, N, K):
     return _lib.GemmCfg(k, waves, depth, ks, strips)
 
 
+def grouped_gemv_case(rng, L, orc, dev):
+    """One grouped M = 1 launch in the decode GEMV's domain; returns (mismatch records, label)."""
+    K = 2048 * int(rng.integers(1, 5))
+    dt = "bf16" if rng.random() < 0.6 else "f16"
+    cfg = None
+    if rng.random() < 0.5:
+        cfg = _lib.GemmCfg(_lib.GEMM_GEMV, int(rng.choice([8, 16])), int(rng.choice([1, 2, 4])), 1,
+                           int(rng.choice([0, 1, 2])))
+    limit = (8192 if cfg is not None else 4096) // 64
+    count = int(rng.integers(2, 5))
+    cuts = np.sort(rng.choice(np.arange(1, int(rng.integers(count, limit + 1))), count - 1, replace=False))
+    widths = np.diff(np.concatenate([[0], cuts, [cuts[-1] + int(rng.integers(1, limit - cuts[-1] + 1))]]))
+    Ns = [64 * int(w) for w in widths]
+    assert len(Ns) == count and all(n > 0 for n in Ns) and sum(Ns) <= 64 * limit
+    bpr, groups = K // 64, -(-(K // 64) // 4)
+    seed = int(rng.integers(1, 1 << 30))
+    x = O.normal_f32(seed + 1, K, stream=9).reshape(1, K)
+    xt = torch.from_numpy(x).to(torch.bfloat16 if dt == "bf16" else torch.float16)
+    xb = xt.view(torch.int16).numpy().view(np.uint16)
+    xf = bits_to_f64(xb, dt)
+    xd = xt.to(dev)
+    mats = (_lib.GemmMat * count)()
+    keep, ys, refs, ovs = [], [], [], []
+    for i, N in enumerate(Ns):
+        ov = {"a2_kind": "normal" if rng.random() < 0.5 else "uniform"}
+        if rng.random() < 0.3:  # the statistics of a few rows, repeating: a wrap at row boundaries only
+            ov["nb"] = bpr * int(rng.integers(1, N + 1))
+            ov["n2"] = groups * int(rng.integers(1, N + 1))
+        ovs.append(ov)
+        p, a1, a2, _ = O.golden_case_inputs(N, K, seed + 7 * i, ov)
+        wf = bits_to_f64(orc.dequant_ref(p, a1, a2, N, K, O.BF16 if dt == "bf16" else O.F16), dt)
+        ref = xf @ wf.T
+        refs.append((ref, tol(ref, np.abs(xf) @ np.abs(wf).T, dt)))
+        t = [torch.from_numpy(v).to(dev) for v in (p, a1, a2)]
+        keep.append(t)
+        y = torch.full((1, N), float("nan"), dtype=xt.dtype, device=dev)
+        ys.append(y)
+        mats[i] = _lib.GemmMat(t[0].data_ptr(), t[0].numel(), t[1].data_ptr(), t[1].numel(), t[2].data_ptr(),
+                               t[2].numel(), y.data_ptr(), N)
+    cp = ctypes.byref(cfg) if cfg is not None else None
+    wsz = L.nf4_gemm_grouped_workspace_bytes(1, K, mats, count, cp)
+    ws = torch.zeros(max(wsz, 16), dtype=torch.uint8, device=dev)
+    sp = torch.cuda.current_stream().cuda_stream
+    rc = L.nf4_gemm_ref_grouped(xd.data_ptr(), 1, K, mats, count, _lib.BF16 if dt == "bf16" else _lib.F16,
+                                ws.data_ptr() if wsz else None, wsz, cp, sp)
+    label = [cfg.kernel, cfg.waves, cfg.depth, cfg.ksplit, cfg.strips] if cfg is not None else "default"
+    info = {"grouped": Ns, "K": K, "dtype": dt, "seed": seed, "ov": ovs, "path": label}
+    if rc:
+        return [dict(info, rc=int(rc))], label
+    out = []
+    if wsz and L.nf4_gemm_check_workspace(ws.data_ptr(), wsz, sp):
+        out.append(dict(info, timeout=True))
+    for i, (y, (ref, bound)) in enumerate(zip(ys, refs)):
+        got = bits_to_f64(y.view(torch.int16).cpu().numpy().view(np.uint16), dt).reshape(1, Ns[i])
+        if not (np.abs(got - ref) <= bound).all():
+            fin = np.abs(got - ref)[np.isfinite(got)]
+            out.append(dict(info, weight=i, worst=float(fin.max()) if fin.size else None,
+                            nan=int(np.isnan(got).sum())))
+    return out, label
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", type=int, default=1500)
@@ -71,7 +135,8 @@ def main():
     ap.add_argument("--seconds", type=float, default=500.0)
     ap.add_argument("--cfg-rate", type=float, default=0.25, help="share of cases that also run a drawn configuration")
     ap.add_argument("--gemv-rate", type=float, default=0.0,
-                    help="share of cases at M = 1 with K % 2048 == 0 and N <= 4096 (the decode GEMV's domain)")
+                    help="share of cases at M = 1 with K % 2048 == 0 and N <= 4096 (the decode GEMV's domain); "
+                         "half of them grouped launches of 2-4 weights")
     ap.add_argument("--boundary-rate", type=float, default=0.1,
                     help="share of cases drawn from the default-rule boundary shapes (large N, K = 14336)")
     args = ap.parse_args()
@@ -80,7 +145,13 @@ def main():
     orc = O.COracle()
     rng = np.random.default_rng(args.seed)
     t0 = time.time()
-    done = bad = cfg_runs = 0
+    done = bad = cfg_runs = grouped_runs = 0
+
+    def progress():
+        if done % 100 == 0:
+            print(json.dumps({"progress": done, "mismatches": bad, "cfg_runs": cfg_runs, "grouped_runs": grouped_runs,
+                              "seconds": round(time.time() - t0, 1)}), flush=True)
+
     for i in range(args.cases):
         if time.time() - t0 > args.seconds:
             break
@@ -95,6 +166,15 @@ def main():
             N, K = [(1024, 4096), (4096, 4096), (8192, 4096), (14336, 4096), (24576, 4096), (28672, 4096),
                     (4096, 14336), (1024, 14336)][int(rng.integers(0, 8))]
         if rng.random() < args.gemv_rate:
+            if rng.random() < 0.5:
+                records, _label = grouped_gemv_case(rng, L, orc, dev)
+                for r in records:
+                    bad += 1
+                    print(json.dumps({"mismatch": r}), flush=True)
+                grouped_runs += 1
+                done += 1
+                progress()
+                continue
             M, N, K = 1, 64 * int(rng.integers(1, 65)), 2048 * int(rng.integers(1, 9))
         dt = "bf16" if rng.random() < 0.6 else "f16"
         nb_full = N * K // 64
@@ -139,10 +219,9 @@ def main():
                                                "path": label,
                                                "worst": float(np.abs(got - ref).max())}}), flush=True)
         done += 1
-        if done % 100 == 0:
-            print(json.dumps({"progress": done, "mismatches": bad, "cfg_runs": cfg_runs,
-                              "seconds": round(time.time() - t0, 1)}), flush=True)
-    print(json.dumps({"summary": {"cases": done, "explicit_cfg_runs": cfg_runs, "mismatches": bad,
+        progress()
+    print(json.dumps({"summary": {"cases": done, "explicit_cfg_runs": cfg_runs, "grouped_runs": grouped_runs,
+                                  "mismatches": bad,
                                   "seed": args.seed, "seconds": round(time.time() - t0, 1)}}), flush=True)
 
 
