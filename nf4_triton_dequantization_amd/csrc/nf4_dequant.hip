@@ -29,7 +29,9 @@
 //    up in the 16-entry LDS table and stores the product unrounded.
 //  * the default grid gives every wave exactly one tile (tiles/4 workgroups), which it
 //    runs straight through; only a grid capped through nf4_dequant_ref_cfg makes waves
-//    walk several tiles in the software-pipelined loop.
+//    walk several tiles in the software-pipelined loop.  One matrix under the default
+//    grid runs nf4_flat1_kernel: that one-tile path with scalar arguments, the first 14
+//    dwords of them preloaded into SGPRs at wave launch.
 //  * batched: up to NF4DQ_BATCH_MAX matrices per launch in the kernel
 //    arguments; a wave finds its matrix by scanning scalar tile offsets.
 //  * "chunk" kernels (round 5): any other shape (partial blocks, padded rows, odd n,
@@ -92,7 +94,7 @@ struct Batch {
 #define NF4_FSTAMP(slot_, val_)                                                                      \
     do {                                                                                             \
         __builtin_amdgcn_sched_barrier(0);                                                           \
-        if (lane == 0) bt.stamps[(blockIdx.x * kFlatWaves + (threadIdx.x >> 6)) * 4u + (slot_)] = (val_); \
+        if (lane == 0) stamps[(blockIdx.x * kFlatWaves + (threadIdx.x >> 6)) * 4u + (slot_)] = (val_);    \
         __builtin_amdgcn_sched_barrier(0);                                                           \
     } while (0)
 #define NF4_FNOW() __builtin_amdgcn_s_memrealtime()
@@ -135,6 +137,12 @@ __device__ __forceinline__ void store1(void* out, int64_t i, float x) {
 //                       loads, dropped-store burst); 7.33 -> 7.22 us per streamed 4096^2
 //                       launch at K = 128 (profiles/r05/single_tile_fast_path_ab.jsonl)
 //   NF4_DQ_ABL_NOSCALE  ablation (wrong results, tools only): no absmax / nested-absmax loads
+//   NF4_DQ_FLAT1        1 (product): one matrix under an uncapped grid goes to nf4_flat1_kernel
+//                       (scalar arguments, kernarg preload); 0 = nf4_flat_kernel<.., 1> as before
+//                       (profiles/flat1/)
+#ifndef NF4_DQ_FLAT1
+#define NF4_DQ_FLAT1 1
+#endif
 #ifndef NF4_DQ_FLAT_WAVES
 #define NF4_DQ_FLAT_WAVES 4
 #endif
@@ -216,7 +224,9 @@ __device__ __forceinline__ uint32_t tile_block(const Desc& D, uint32_t base, uin
 
 // Issue the loads of tile `base` (packed bytes) of matrix D.  Buffer loads
 // outside the matrix return 0, so partial tiles need no predicates.
-template <int DT, int MODE>
+// FENCE (nf4_flat1_kernel): nothing below the packed loads is scheduled above them, so
+// they issue from the preloaded kernel arguments before any wait on scalar memory.
+template <int DT, int MODE, bool FENCE = false>
 __device__ __forceinline__ TileIn tile_load(const Desc& D, __amdgpu_buffer_rsrc_t rp, uint32_t base, uint32_t lane) {
     constexpr uint32_t LB = lane_bytes<DT>();
     TileIn in;
@@ -231,7 +241,10 @@ __device__ __forceinline__ TileIn tile_load(const Desc& D, __amdgpu_buffer_rsrc_
             }
         }
     };
-    if constexpr (!NF4_DQ_SCALE_FIRST) packed_loads();
+    if constexpr (!NF4_DQ_SCALE_FIRST) {
+        packed_loads();
+        if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
+    }
     const uint32_t g = tile_block<DT>(D, base, lane);
     if constexpr (NF4_DQ_ABL_NOSCALE) {
         in.a1 = g & 255u;
@@ -416,6 +429,7 @@ __global__ __launch_bounds__(kFlatWg) void nf4_flat_kernel(const Batch<MAXB> bt)
 #if NF4_FLAT_STAMPS
     const unsigned long long t_entry = NF4_FNOW();
     unsigned long long tiles_done = 0;
+    unsigned long long* const stamps = bt.stamps;
 #endif
     const uint32_t t0 = __builtin_amdgcn_readfirstlane(blockIdx.x * kFlatWaves + (threadIdx.x >> 6));
     const uint32_t nwaves = gridDim.x * kFlatWaves;
@@ -516,6 +530,85 @@ __global__ __launch_bounds__(kFlatWg) void nf4_flat_kernel(const Batch<MAXB> bt)
     NF4_FSTAMP(0, t_entry);
     NF4_FSTAMP(2, NF4_FNOW());
     NF4_FSTAMP(3, tiles_done);
+#endif
+}
+
+// The flat kernel of one matrix under the default, uncapped grid (NF4_DQ_FLAT1): every
+// wave owns exactly one tile, so the body is nf4_flat_kernel's one-tile path and nothing
+// else.  The arguments are scalars in first-use order instead of a Batch struct: the
+// first 14 dwords (everything up to bpr_d) arrive in SGPRs at wave launch (kernarg
+// preload, -mllvm -amdgpu-kernarg-preload-count=14; a by-value struct is never
+// preloaded), and the packed loads need only those, so they issue before the wave's
+// first wait on scalar memory.  No gridDim read: the hidden arguments are scalar loads too.
+template <int DT, int MODE>
+__global__ __launch_bounds__(kFlatWg) void nf4_flat1_kernel(
+    const uint32_t* packed, uint32_t nbytes, uint32_t tiles, u32x4* out,  // the packed loads (and the stores)
+    const uint8_t* a1, const float* a2, uint32_t blk_shift, uint32_t blk_base, uint32_t groups, uint32_t bpr_d,
+    uint32_t bpr_mul, uint32_t bpr_shift, uint32_t nb_d, uint32_t nb_mul, uint32_t nb_shift, uint32_t n2_d,
+    uint32_t n2_mul, uint32_t n2_shift, const float* code2, float offset, uint32_t blk2_shift
+#if NF4_FLAT_STAMPS
+    , unsigned long long* stamps
+#endif
+) {
+    __shared__ __attribute__((aligned(16))) float lut[16];
+    __shared__ __attribute__((aligned(16))) float code2s[MODE == kBnb ? 256 : 1];
+    constexpr bool kTbl = NF4_DQ_DECODE == 1 && DT != NF4DQ_F32;
+    __shared__ __attribute__((aligned(256))) char tbl[kTbl ? kFlatWaves * 2048 : 4];
+    const uint32_t lane = threadIdx.x & 63u;
+#if NF4_FLAT_STAMPS
+    const unsigned long long t_entry = NF4_FNOW();
+#endif
+    const uint32_t t0 = __builtin_amdgcn_readfirstlane(blockIdx.x * kFlatWaves + (threadIdx.x >> 6));
+    const bool valid = t0 < tiles;
+    // past the end: an offset beyond every buffer range (loads return 0, no traffic)
+    const uint32_t base = valid ? t0 * tile_bytes<DT>() : 0xFFFFF000u;
+    Desc D;
+    D.packed = packed;
+    D.a1 = a1;
+    D.a2 = a2;
+    D.code2 = code2;
+    D.out = out;
+    D.offset = offset;
+    D.nbytes = nbytes;
+    D.tile_begin = 0u;
+    D.groups = groups;
+    D.nb = FastDiv{nb_d, nb_mul, nb_shift};
+    D.n2 = FastDiv{n2_d, n2_mul, n2_shift};
+    D.bpr = FastDiv{bpr_d, bpr_mul, bpr_shift};
+    D.blk_shift = blk_shift;
+    D.blk2_shift = blk2_shift;
+    D.blk_base = blk_base;
+    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)packed, 0, nbytes, kRsrcFlags);
+    const __amdgpu_buffer_rsrc_t ro =
+        __builtin_amdgcn_make_buffer_rsrc((void*)out, 0, nbytes * out_bytes_per_packed_byte<DT>(), kRsrcFlags);
+    const TileIn A = tile_load<DT, MODE, true>(D, rp, base, lane);
+    write_lut(lut);
+    if constexpr (MODE == kBnb) {  // the code pointer is past the preloaded arguments: behind the tile's loads
+        for (uint32_t i = threadIdx.x; i < 256u; i += kFlatWg) code2s[i] = code2[i];
+    }
+    __syncthreads();
+    if (!valid) {  // a wave past the end of the matrix: through the barrier, nothing written
+        NF4_FSTAMP(0, t_entry);
+        NF4_FSTAMP(1, 0ull);
+        NF4_FSTAMP(2, NF4_FNOW());
+        NF4_FSTAMP(3, 0ull);
+        return;
+    }
+    if constexpr (kTbl) {
+        TblCtx tc;
+        tc.tbl = tbl;
+        tc.tb = ((threadIdx.x >> 6) << 11) + ((lane >> 3) << 8);
+        tc.c01 = *reinterpret_cast<const f32x2*>(lut + 2u * (lane & 7u));
+        tile_finish_tbl<DT, MODE>(D, ro, A, base, lane, code2s, tc);
+    } else {
+        tile_finish<DT, MODE>(D, ro, lut, A, base, lane, code2s);
+    }
+#if NF4_FLAT_STAMPS
+    NF4_FSTAMP(1, NF4_FNOW());
+    __builtin_amdgcn_s_waitcnt(0);
+    NF4_FSTAMP(0, t_entry);
+    NF4_FSTAMP(2, NF4_FNOW());
+    NF4_FSTAMP(3, 1ull);
 #endif
 }
 
@@ -1424,8 +1517,23 @@ int cu_count() {
     return cus;
 }
 
+// one_tile: the default grid, every wave owns at most one tile.
 template <int DT, int MODE, int MAXB>
-void launch_one(const Batch<MAXB>& b, uint64_t blocks, hipStream_t st) {
+void launch_one(const Batch<MAXB>& b, uint64_t blocks, bool one_tile, hipStream_t st) {
+    if constexpr (MAXB == 1 && NF4_DQ_FLAT1) {
+        if (one_tile) {
+            const Desc& d = b.d[0];
+            nf4_flat1_kernel<DT, MODE><<<dim3((unsigned)blocks), dim3(kFlatWg), 0, st>>>(
+                d.packed, d.nbytes, b.total_tiles, d.out, d.a1, d.a2, d.blk_shift, d.blk_base, d.groups, d.bpr.d,
+                d.bpr.mul, d.bpr.shift, d.nb.d, d.nb.mul, d.nb.shift, d.n2.d, d.n2.mul, d.n2.shift, d.code2, d.offset,
+                d.blk2_shift
+#if NF4_FLAT_STAMPS
+                , b.stamps
+#endif
+            );
+            return;
+        }
+    }
     hipLaunchKernelGGL((nf4_flat_kernel<DT, MODE, MAXB>), dim3((unsigned)blocks), dim3(kFlatWg), 0, st, b);
 }
 
@@ -1445,6 +1553,10 @@ int launch_flat_batch(const Batch<MAXB>& bt, int dtype, int mode, const nf4_laun
     b.total_tiles = acc;
     if (acc == 0) return NF4DQ_OK;
     uint64_t blocks = (acc + kFlatWaves - 1) / kFlatWaves;
+    // nf4_flat1_kernel for the default grid only: a call that names a cap (nf4_dequant_ref_cfg)
+    // keeps nf4_flat_kernel whether or not the cap binds, so tuning runs and the tests have
+    // the loop kernel to compare against at any size
+    const bool one_tile = cfg.blocks_per_cu <= 0;
     if (cfg.blocks_per_cu > 0) {
         const uint64_t cap = (uint64_t)cfg.blocks_per_cu * (uint64_t)cu_count();
         if (blocks > cap) blocks = cap;
@@ -1452,14 +1564,14 @@ int launch_flat_batch(const Batch<MAXB>& bt, int dtype, int mode, const nf4_laun
 #if NF4_FLAT_STAMPS
     b.stamps = g_stamps;
 #endif
-#define NF4_D(DT_)                                                              \
-    do {                                                                        \
-        switch (mode) {                                                         \
-            case kRef: launch_one<DT_, kRef, MAXB>(b, blocks, st); break;       \
-            case kSingle: launch_one<DT_, kSingle, MAXB>(b, blocks, st); break; \
-            case kBnb: launch_one<DT_, kBnb, MAXB>(b, blocks, st); break;       \
-            default: launch_one<DT_, kBnbSingle, MAXB>(b, blocks, st); break;   \
-        }                                                                       \
+#define NF4_D(DT_)                                                                        \
+    do {                                                                                  \
+        switch (mode) {                                                                   \
+            case kRef: launch_one<DT_, kRef, MAXB>(b, blocks, one_tile, st); break;       \
+            case kSingle: launch_one<DT_, kSingle, MAXB>(b, blocks, one_tile, st); break; \
+            case kBnb: launch_one<DT_, kBnb, MAXB>(b, blocks, one_tile, st); break;       \
+            default: launch_one<DT_, kBnbSingle, MAXB>(b, blocks, one_tile, st); break;   \
+        }                                                                                 \
     } while (0)
     if (dtype == NF4DQ_BF16) NF4_D(NF4DQ_BF16);
     else if (dtype == NF4DQ_F16) NF4_D(NF4DQ_F16);

@@ -18,6 +18,8 @@
 // gather delays (at 414c083), bitsandbytes-mode code-table loads and gather
 // delays (at 99ed841), and the chunk kernel's barrier / scale-gather placements (at 1601634).
 //   DQV_SINGLE=1   one-tile waves skip the pipelined loop
+//   DQV_FLAT1=0    one matrix under an uncapped grid stays on nf4_flat_kernel (struct argument,
+//              no kernarg preload) instead of nf4_flat1_kernel
 //   DQV_FE=n   chunk kernel's LDS-staged flush (NF4_DQ_FLUSH_EDGE: 1 edge lines default policy,
 //              2 no end-piece element stores (timing only), 3 all flush stores default policy);
 //              measured in round 6 (profiles/r06/chunk/s3_flush_variants.jsonl), the hook removed
@@ -57,6 +59,9 @@
 #endif
 #ifdef DQV_SINGLE
 #define NF4_DQ_SINGLE_FAST DQV_SINGLE
+#endif
+#ifdef DQV_FLAT1
+#define NF4_DQ_FLAT1 DQV_FLAT1
 #endif
 #ifdef DQV_DEC
 #define NF4_DQ_DECODE DQV_DEC

@@ -1,6 +1,7 @@
 """Per-wave phase timing of the flat dequant kernel (diagnostic build `make -C tools stamps`).
 
     python tools/flat_stamps.py [--shape 4096,4096] [--reps 8] [--flags 0] [--tile-dwords 4]
+                                [--lib tools/_build/libnf4dq_stamps.so]
 
 Each wave stamps s_memrealtime (100 MHz, 10 ns ticks) at entry, after its first
 tile is decoded and its stores issued (= its first loads arrived), and at exit
@@ -44,12 +45,14 @@ def main():
     ap.add_argument("--stream", type=int, default=0,
                     help="round 5: stamp the last of this many back-to-back launches (HBM-streamed "
                          "rotation, bench.py's regime) and the one before it, instead of cold single launches")
+    ap.add_argument("--lib", default=os.path.join(REPO, "tools", "_build", "libnf4dq_stamps.so"),
+                    help="the stamped build to load (another commit's, for an A/B of stamps)")
     args = ap.parse_args()
     if args.stream:
         return stream_main(args)
     # the diagnostic build beside the product one (the package import already
     # loaded libnf4dq.so); only the two entry points used here are bound
-    L = ctypes.CDLL(os.path.join(REPO, "tools", "_build", "libnf4dq_stamps.so"))
+    L = ctypes.CDLL(os.path.abspath(args.lib))
     L.nf4_dequant_ref_cfg.restype = ctypes.c_int
     L.nf4_dequant_ref_cfg.argtypes = _lib.SIGNATURES["nf4_dequant_ref_cfg"][1]
     L.nf4_dbg_set_stamps.argtypes = [ctypes.c_void_p]
@@ -102,7 +105,7 @@ def stream_main(args):
     inputs and outputs rotated independently): the last two launches of a run of
     ``--stream`` write their stamps to two buffers, so the boundary between them is seen
     from the waves' side (last wave exit of launch L-1 -> first wave entry of launch L)."""
-    L = ctypes.CDLL(os.path.join(REPO, "tools", "_build", "libnf4dq_stamps.so"))
+    L = ctypes.CDLL(os.path.abspath(args.lib))
     L.nf4_dequant_ref.restype = ctypes.c_int
     L.nf4_dequant_ref.argtypes = _lib.SIGNATURES["nf4_dequant_ref"][1]
     L.nf4_dbg_set_stamps.argtypes = [ctypes.c_void_p]
@@ -152,7 +155,8 @@ def stream_main(args):
                      "boundary": (t0 - prev[:, 2].max()) / 100.0,
                      "prev_span": (prev[:, 2].max() - prev[:, 0].min()) / 100.0})
     agg = {k: np.concatenate([np.atleast_1d(r[k]) for r in rows]) for k in rows[0]}
-    print(json.dumps({"shape": [m, n], "mode": f"stream: last of {args.stream} back-to-back launches",
+    print(json.dumps({"lib": os.path.basename(args.lib), "shape": [m, n],
+                      "mode": f"stream: last of {args.stream} back-to-back launches",
                       "in_sets": pin, "out_sets": pout, "waves": int(len(rows[-1]["entry"])),
                       "entry_us": pct(agg["entry"]), "first_tile_stored_minus_entry_us": pct(agg["first"]),
                       "first_tile_stored_us": pct(agg["first_abs"]), "exit_us": pct(agg["exit"]),
