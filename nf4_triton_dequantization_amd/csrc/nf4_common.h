@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/nf4_dequant.h"
+#include "nf4_fastdiv.h"
 
 namespace nf4dq {
 
@@ -15,20 +16,7 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-// Division by a run-time constant for n < 2^31: q = (umulhi(n, mul) + n) >> shift.
-struct FastDiv {
-    uint32_t d, mul, shift;
-};
-
-inline FastDiv make_fastdiv(uint32_t d) {
-    FastDiv f{d, 0u, 0u};
-    uint32_t s = 0;
-    while (s < 32 && (uint64_t(1) << s) < d) ++s;
-    f.shift = s;
-    f.mul = uint32_t(((uint64_t(1) << 32) * ((uint64_t(1) << s) - d)) / d + 1);
-    return f;
-}
-
+// FastDiv (nf4_fastdiv.h) on the device: q = (umulhi(n, mul) + n) >> shift.
 __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) {
     return (__umulhi(n, f.mul) + n) >> f.shift;
 }

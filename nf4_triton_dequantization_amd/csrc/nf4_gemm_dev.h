@@ -45,10 +45,12 @@
 
 #include "../../include/nf4_dequant.h"
 #include "nf4_common.h"
+#include "nf4_gemm_plan.h"
 
 namespace {
 
 using namespace nf4dq;
+using namespace nf4gemm;  // the constants shared with the host plan
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -148,7 +150,6 @@ constexpr uint32_t kOob = 0x80000000u;  // beyond every buffer range: loads retu
 // would read that stale entry as written; so while the word is set every reducer
 // writes NaN instead of its sum, until the host's check re-zeroes the workspace.
 constexpr int kSpinMax = 1 << 16;
-constexpr uint32_t kErrWord = 16384;  // uint32 index in the workspace header (byte 64 KiB)
 
 // A partial's bits on the wire: its NOT, except that the one NaN whose NOT would be
 // 0 (0xFFFFFFFF) goes as the NaN 0x7FFFFFFF -- so a written half is never 0 and a
@@ -311,11 +312,9 @@ __device__ __forceinline__ void store_y(void* y, uint32_t i, float v) {
         reinterpret_cast<_Float16*>(y)[i] = (_Float16)opaque(v);
     }
 }
-constexpr uint32_t kChunkK = 128;
 
 // One weight of a 128-deep launch; weights that share x (q/k/v, gate/up) go in
 // one launch, column groups numbered over all of them.
-constexpr int kK128GroupMax = 8;
 struct K128Mat {
     const uint8_t* packed;  // [N][K/2]
     const uint8_t* a1;      // [nb]
@@ -1270,14 +1269,9 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(1, 2)))
 // scale) of row nl, i.e. eight MFMA B fragments.  Waves of a workgroup split
 // the strip's K slice (interleaved chunks, so neighbouring waves read
 // neighbouring lines) and T strips; partial sums meet in LDS in a fixed order.
-constexpr uint32_t kSChunkK = 256;
-
-constexpr int kXR = 8;               // x staging: 16-byte pieces per thread and row tile
-constexpr uint32_t kLdsX = 0;        // dynamic LDS: [x slice][zero block][partials]
 
 // One weight of a launch.  Several weights that share x (q/k/v, gate/up) go in
 // one launch: workgroups are numbered over all their strip groups.
-constexpr int kGroupMax = 8;
 struct StreamMat {
     const uint8_t* packed;
     const uint8_t* a1;
@@ -1316,8 +1310,6 @@ struct SSlot {
     uint32_t qa;
     float qb;
 };
-
-constexpr int kVsMax = 16;  // chunks per wave covered by the vector-scale form  // beyond every buffer range: loads return 0, no traffic
 
 template <bool VS>
 __device__ __forceinline__ void sslot_issue(const StreamArgs& A, const StreamMat& Mt, __amdgpu_buffer_rsrc_t rw,

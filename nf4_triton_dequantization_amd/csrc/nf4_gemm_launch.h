@@ -1,0 +1,104 @@
+// nf4_gemm_launch.h -- launcher side of the fused GEMM: the interface between the host
+// dispatch (nf4_gemm.hip) and the per-family launchers (nf4_gemm_launch_*.hip), and what
+// the launchers share: the CU count, the kernel-argument fills, the template dispatch
+// and the launch itself.  The plan they carry out is in nf4_gemm_plan.h.
+#pragma once
+
+#include <type_traits>
+
+#include "nf4_gemm_dev.h"
+
+namespace nf4gemm {
+
+// Launchers (shapes and cfg validated and known to run by the dispatch; workspace sized
+// by it; cus = device_cus(), which the plan was made for).  They return NF4DQ_OK or a HIP
+// code; NF4DQ_ERR_ARG only for a plan that cannot run, which the dispatch never sends.
+int launch_stream(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
+                  const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st);
+int launch_persist(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
+                   const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st);
+int launch_xs(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
+              const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st);
+int launch_xr(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
+              const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st);
+int launch_k128(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
+                const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st);
+int launch_gemv(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
+                const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st);
+
+}  // namespace nf4gemm
+
+namespace {
+
+using nf4gemm::HostMat;
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+inline int hip_rc2(hipError_t e) { return e == hipSuccess ? NF4DQ_OK : NF4DQ_ERR_HIP_BASE + (int)e; }
+
+// CUs of the current device (256 where it cannot be asked).
+inline int device_cus() {
+    static int cached[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (!cached[dev]) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        cached[dev] = n;
+    }
+    return cached[dev];
+}
+
+// The header fields every family's argument struct has.
+template <class Args>
+inline void fill_common(Args& a, int count, const void* x, int64_t M, int64_t K, const nf4_gemm_cfg& cfg,
+                        void* workspace) {
+    a.nmat = (uint32_t)count;
+    a.x = x;
+    a.counters = reinterpret_cast<uint32_t*>(workspace);
+    a.slab = cfg.ksplit > 1 ? reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) + kHeaderBytes) : nullptr;
+    a.M = (uint32_t)M;
+    a.K = (uint32_t)K;
+    a.ksplit = (uint32_t)cfg.ksplit;
+    a.bpr = (uint32_t)(K / 64);
+    a.groups = (a.bpr + 3) / 4;
+}
+
+// One weight's pointers, N and absmax divisors.  The divisors are clamped, nb at 2^31
+// and n2 at 2^29 (its byte length fits 32 bits): an nb index is below N * K / 64 < 2^26 and
+// an n2 index below N * ceil(K / 256) <= packed_len / 64 < 2^25, so at or above either
+// clamp nothing ever wraps and the clamped divisor gives the same remainders.
+template <class Mat>
+inline void fill_mat(Mat& m, const HostMat& h) {
+    m.packed = h.packed;
+    m.a1 = h.a1;
+    m.a2 = h.a2;
+    m.y = h.y;
+    m.N = (uint32_t)h.N;
+    m.nb = make_fastdiv((uint32_t)(h.nb > (int64_t(1) << 31) ? (int64_t(1) << 31) : h.nb));
+    m.n2 = make_fastdiv((uint32_t)(h.n2 > (int64_t(1) << 29) ? (int64_t(1) << 29) : h.n2));
+}
+
+// Run-time value -> template argument: f(integral_constant<V>) for the first V equal to
+// v, the last V when none is (cfg validity has ruled the rest out).
+template <auto V, auto... Rest, class F>
+inline void pick(decltype(V) v, F&& f) {
+    if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<decltype(V), V>{});
+    else if (v == V) f(std::integral_constant<decltype(V), V>{});
+    else pick<Rest...>(v, f);
+}
+
+// Opt in once per kernel to dynamic LDS up to `cap` (static + dynamic above 64 KiB needs
+// it), then launch.
+template <auto Kernel, class Args>
+inline void launch_lds(uint32_t cap, dim3 grid, dim3 block, uint32_t dyn, hipStream_t st, const Args& a) {
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)cap);
+        attr = true;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, dyn, st, a);
+}
+
+}  // namespace

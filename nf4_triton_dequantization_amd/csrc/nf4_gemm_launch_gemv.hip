@@ -22,7 +22,7 @@
 // Scales: block b = 32 j + l / 2 of the row: a1[(row bpr) mod nb + b], a2[(row groups)
 // mod n2 + b / 4] (absmax not wrapping inside a row, as the persistent kernel assumes),
 // s = (a1 / 127) * a2 (IEEE; the q/127 table), as kernel_optimized.py:40-45, :97-98.
-#include "nf4_gemm_plan.h"
+#include "nf4_gemm_launch.h"
 
 namespace {
 
@@ -275,18 +275,13 @@ __global__ __launch_bounds__(64 * W) void nf4_gemv_kernel(const GemvArgs A) {
 
 namespace nf4gemm {
 
-// LDS: the x staging (2 K bytes) beside the 64 KiB pair table and the q/127 table.
-uint32_t gemv_lds_bytes(int64_t K) { return (uint32_t)(K * 2); }
-
 // One launch over `count` weights sharing x (M = 1; K % 2048 == 0; absmax not wrapping
 // inside a row).  cfg.waves: waves per workgroup (8 / 16); cfg.depth: rows per row group R
 // (1 / 2 / 4); cfg.strips: workgroups per CU in the grid (0 / 1 / 2, 0 = 1), at most one
 // row group per wave.
 int launch_gemv(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
-                const nf4_gemm_cfg& cfg, hipStream_t st) {
-    if (M != 1 || K % kGvPiece || K > 16384) return NF4DQ_ERR_ARG;
-    if (cfg.waves != 8 && cfg.waves != 16) return NF4DQ_ERR_ARG;
-    if (cfg.depth != 1 && cfg.depth != 2 && cfg.depth != 4) return NF4DQ_ERR_ARG;
+                const nf4_gemm_cfg& cfg, void*, int cus, hipStream_t st) {
+    if (M != 1 || cfg_runs(cfg, M, K, mats, count, cus) != NF4DQ_OK) return NF4DQ_ERR_ARG;  // not a plan
     GemvArgs A{};
     A.nmat = (uint32_t)count;
     A.x = x;
@@ -294,63 +289,25 @@ int launch_gemv(const HostMat* mats, int count, const void* x, int64_t M, int64_
     A.J = (uint32_t)(K / kGvPiece);
     A.bpr = (uint32_t)(K / 64);
     A.groups = (A.bpr + 3) / 4;
-    const uint32_t R = (uint32_t)cfg.depth;
     uint32_t rows = 0;
     for (int i = 0; i < count; ++i) {
-        const HostMat& h = mats[i];
-        if (!(h.nb % (K / 64) == 0 || h.nb >= h.N * (K / 64)) ||
-            !(h.n2 % (int64_t)A.groups == 0 || h.n2 >= h.N * (int64_t)A.groups))
-            return NF4DQ_ERR_ARG;  // absmax wrapping inside a row
-        if (h.N % R) return NF4DQ_ERR_ARG;
         GemvMat& m = A.mat[i];
-        m.packed = h.packed;
-        m.a1 = h.a1;
-        m.a2 = h.a2;
-        m.y = h.y;
-        m.N = (uint32_t)h.N;
+        fill_mat(m, mats[i]);
         m.row_begin = rows;
-        const int64_t nbc = h.nb > (int64_t(1) << 31) ? (int64_t(1) << 31) : h.nb;
-        const int64_t n2c = h.n2 > (int64_t(1) << 29) ? (int64_t(1) << 29) : h.n2;
-        m.nb = make_fastdiv((uint32_t)nbc);
-        m.n2 = make_fastdiv((uint32_t)n2c);
-        m.nb_bytes = (uint32_t)nbc;
-        m.n2_bytes = (uint32_t)(n2c * 4);
-        rows += (uint32_t)h.N;
+        m.nb_bytes = m.nb.d;
+        m.n2_bytes = m.n2.d * 4u;
+        rows += m.N;
     }
-    A.groups_total = rows / R;
-    const uint32_t W = (uint32_t)cfg.waves;
-    uint32_t G = (uint32_t)device_cus() * (cfg.strips > 0 ? (uint32_t)cfg.strips : 1u);
-    const uint32_t need = (A.groups_total + W - 1) / W;
-    if (G > need) G = need;
-    if (G < 1) G = 1;
-    const uint32_t dyn = gemv_lds_bytes(K);
-    const dim3 grid(G), block(64 * W);
-#define NF4_GV(DT_, W_, R_)                                                                                     \
-    do {                                                                                                        \
-        static bool attr_ = false;                                                                              \
-        if (!attr_) {                                                                                           \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nf4_gemv_kernel<DT_, W_, R_>),              \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 65536);                       \
-            attr_ = true;                                                                                       \
-        }                                                                                                       \
-        hipLaunchKernelGGL((nf4_gemv_kernel<DT_, W_, R_>), grid, block, dyn, st, A);                            \
-    } while (0)
-#define NF4_GVR(DT_, W_)                        \
-    do {                                        \
-        if (R == 1) NF4_GV(DT_, W_, 1);         \
-        else if (R == 2) NF4_GV(DT_, W_, 2);    \
-        else NF4_GV(DT_, W_, 4);                \
-    } while (0)
-#define NF4_GVW(DT_)                            \
-    do {                                        \
-        if (W == 8) NF4_GVR(DT_, 8);            \
-        else NF4_GVR(DT_, 16);                  \
-    } while (0)
-    if (dtype == NF4DQ_BF16) NF4_GVW(NF4DQ_BF16);
-    else NF4_GVW(NF4DQ_F16);
-#undef NF4_GVW
-#undef NF4_GVR
-#undef NF4_GV
+    A.groups_total = rows / (uint32_t)cfg.depth;
+    const LaunchShape ls = launch_shape(cfg, M, K, mats, count, cus);
+    const dim3 grid(ls.grid), block(ls.block);
+    pick<NF4DQ_BF16, NF4DQ_F16>(dtype, [&](auto DT) {
+        pick<8, 16>(cfg.waves, [&](auto W) {
+            pick<1, 2, 4>(cfg.depth, [&](auto R) {
+                launch_lds<&nf4_gemv_kernel<DT, W, R>>(65536, grid, block, ls.dyn, st, A);
+            });
+        });
+    });
     return hip_rc2(hipGetLastError());
 }
 

@@ -1118,3 +1118,59 @@ def test_gemv_absmax_wrapping_at_row_boundaries(coracle, gpu, dt, K):
     for i, (y, (ref, tol)) in enumerate(zip(nf4_linear_grouped(x, mods), oracles)):
         check_close_t(y, ref, tol, f"nf4_linear_grouped weight {i}")
     check_close_t(nf4_linear(x, mods[1]), oracles[1][0], oracles[1][1], "nf4_linear")
+
+
+# One smallest shape per kernel family that still has the family's edge (the stream case's
+# fourth K slice is empty): (M, N, K, (kernel, waves, depth, ksplit, strips)).
+_ONE_PATH = [(1, 64, 2048, (7, 16, 1, 1, 0)), (5, 128, 512, (3, 4, 2, 1, 4)), (5, 128, 1280, (2, 4, 2, 4, 1)),
+             (17, 192, 384, (1, 4, 2, 2, 1)), (17, 192, 384, (4, 4, 2, 2, 1)), (32, 128, 512, (5, 8, 2, 1, 1))]
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("M,N,K,cfg", _ONE_PATH)
+def test_single_and_grouped_entries_are_one_path(gpu, dt, M, N, K, cfg):
+    """nf4_gemm_ref_cfg on one weight and nf4_gemm_ref_grouped with count = 1 and the same cfg
+    write bit-identical y, and so do the two library-choice entries (cfg NULL); each call on
+    a workspace of its own size entry, the tickets back at 0 afterwards."""
+    import ctypes
+
+    from nf4_triton_dequantization_amd import _lib
+
+    L = _lib.lib()
+    packed, a1, a2 = O.make_inputs(N, K, seed=N + K + M, a2_kind="normal")
+    t = [torch.from_numpy(v).to(gpu) for v in (packed, a1, a2)]
+    x = _x_bits(M, K, dt, seed=M + 5)[0].to(gpu)
+    tdt, code = (torch.bfloat16, _lib.BF16) if dt == "bf16" else (torch.float16, _lib.F16)
+    st = torch.cuda.current_stream().cuda_stream
+    c = _lib.GemmCfg(*cfg)
+
+    def run(grouped, cfgp):
+        y = torch.full((M, N), float("nan"), dtype=tdt, device=gpu)
+        mats = (_lib.GemmMat * 1)(_lib.GemmMat(t[0].data_ptr(), t[0].numel(), t[1].data_ptr(), t[1].numel(),
+                                               t[2].data_ptr(), t[2].numel(), y.data_ptr(), N))
+        if grouped:
+            wsz = L.nf4_gemm_grouped_workspace_bytes(M, K, mats, 1, cfgp)
+        else:
+            wsz = L.nf4_gemm_workspace_bytes_cfg(M, N, K, cfgp) if cfgp else L.nf4_gemm_workspace_bytes(M, N, K)
+        ws = torch.zeros(max(wsz, 16), dtype=torch.uint8, device=gpu)
+        if grouped:
+            rc = L.nf4_gemm_ref_grouped(x.data_ptr(), M, K, mats, 1, code, ws.data_ptr(), wsz, cfgp, st)
+        elif cfgp:
+            rc = L.nf4_gemm_ref_cfg(x.data_ptr(), M, t[0].data_ptr(), t[0].numel(), t[1].data_ptr(), t[1].numel(),
+                                    t[2].data_ptr(), t[2].numel(), y.data_ptr(), code, N, K, ws.data_ptr(), wsz, cfgp,
+                                    st)
+        else:
+            rc = L.nf4_gemm_ref(x.data_ptr(), M, t[0].data_ptr(), t[0].numel(), t[1].data_ptr(), t[1].numel(),
+                                t[2].data_ptr(), t[2].numel(), y.data_ptr(), code, N, K, ws.data_ptr(), wsz, st)
+        assert rc == 0, _lib.strerror(rc)
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(y).all())  # every output written
+        if wsz:
+            assert int(ws[:65536].view(torch.int32).abs().sum()) == 0  # tickets back at 0
+        return y.view(torch.int16), wsz
+
+    for cfgp in (ctypes.byref(c), None):
+        (y1, w1), (yg, wg) = run(False, cfgp), run(True, cfgp)
+        # (without a cfg the single entry also covers a fallback the grouped one cannot take)
+        assert wg <= w1 and (cfgp is None or (w1 == wg and (w1 > 0) == (c.ksplit > 1)))
+        assert torch.equal(y1, yg)

@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 
 GUARD = 64 * 1024
 PAT = 0xA5
-COUNTER_BYTES = 64 * 1024  # split-K tickets at the head of the GEMM workspace (nf4_gemm.hip kCounterBytes);
+COUNTER_BYTES = 64 * 1024  # split-K tickets at the head of the GEMM workspace (nf4_gemm_plan.h kCounterBytes);
 # the error word and 252 spare bytes follow (kHeaderBytes = 64 KiB + 256), then the slab
 
 

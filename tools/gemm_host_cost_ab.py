@@ -1,0 +1,176 @@
+"""Host-side time per fused-GEMM call of two builds of libnf4dq.so (``--base`` another
+build, e.g. the parent commit's; ``--new`` this tree's by default), interleaved in one
+process: bursts of back-to-back calls on one stream (no sync inside a burst), the host clock
+around the burst; the order of the two alternates burst by burst.
+
+Two routes.  ``abi``: the C entries by ctypes, the same arguments every call (the floor).
+``py``: the package's own ``nf4_linear`` / ``nf4_linear_grouped`` (the whole call: argument
+preparation, output allocation, the ctypes call); the library behind them is switched
+burst by burst through ``_lib._lib``, which both read on every call.
+
+Weights have the real bitsandbytes layout (nb = N K / 64 absmax bytes, n2 = ceil(nb / 256)
+nested scales), so absmax does not wrap inside a row and the library takes its first
+choice: the GEMV at M = 1 up to 4096 columns, the persistent kernel otherwise (``wraps``
+on the line is the plan's predicate in Python; the kernels that ran are named by a
+``rocprofv3 --kernel-trace`` run of the same case with ``--only new --bursts 1``).
+
+``host_us``: per call until the last call returned; ``drained_us``: until the stream
+drained.  host_us is the host's own cost as long as the launch queue never fills: keep the
+bursts short enough (1000 calls: the widest case here returns in 4.7 us per call against
+16.6 us drained, so nothing blocked; where the two are equal the GPU was waiting for the
+host, as on the py route).  One JSON line per case.
+
+    python tools/gemm_host_cost_ab.py --base /path/to/parent/libnf4dq.so --out ab.jsonl
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+from types import SimpleNamespace
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+import nf4_triton_dequantization_amd as P  # noqa: E402
+from nf4_triton_dequantization_amd import _lib  # noqa: E402
+
+CASES = {  # name: (route, M, K, Ns)
+    "abi_single_m1_4096x4096": ("abi", 1, 4096, (4096,)),
+    "abi_grouped_qkv_m1": ("abi", 1, 4096, (4096, 1024, 1024)),
+    "abi_single_m16_4096x4096": ("abi", 16, 4096, (4096,)),
+    "abi_grouped_gate_up_m8": ("abi", 8, 4096, (14336, 14336)),
+    "py_nf4_linear_m1_4096x4096": ("py", 1, 4096, (4096,)),
+    "py_nf4_linear_grouped_qkv_m1": ("py", 1, 4096, (4096, 1024, 1024)),
+}
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--base", default=None, help="the library to compare against")
+ap.add_argument("--new", default=os.path.join(REPO, "nf4_triton_dequantization_amd", "_lib", "libnf4dq.so"))
+ap.add_argument("--out", default="launch_cost_ab.jsonl")
+ap.add_argument("--case", default="all", choices=["all", *CASES])
+ap.add_argument("--calls", type=int, default=1000, help="calls per burst")
+ap.add_argument("--bursts", type=int, default=20, help="timed bursts per library (one more, untimed, first)")
+ap.add_argument("--only", default=None, choices=["new"], help="run this tree's library alone (kernel traces)")
+ARGS = ap.parse_args()
+
+
+def load(path):
+    h = ctypes.CDLL(path)
+    for name, (res, args) in _lib.SIGNATURES.items():
+        if hasattr(h, name):
+            f = getattr(h, name)
+            f.restype = res
+            f.argtypes = args
+    return h
+
+
+LIBS = {"new": load(ARGS.new)}
+if not ARGS.only:
+    if not ARGS.base:
+        ap.error("--base is required unless --only new")
+    LIBS = {"parent": load(ARGS.base), **LIBS}
+dev = torch.device("cuda", 0)
+g = torch.Generator(device="cpu")
+g.manual_seed(1)
+
+
+def weight(N, K):
+    nb = N * K // 64
+    n2 = (nb + 255) // 256
+    packed = torch.randint(0, 256, (N * K // 2,), dtype=torch.uint8, generator=g).to(dev)
+    a1 = torch.randint(1, 256, (nb,), dtype=torch.uint8, generator=g).to(dev)
+    a2 = (torch.rand(n2, generator=g) * 0.1 + 0.01).to(dev)
+    return packed, a1, a2
+
+
+def wraps(N, K, nb, n2):  # nf4_gemm_plan.h no_wrap_in_row, negated
+    bpr = K // 64
+    groups = (bpr + 3) // 4
+    return not ((nb % bpr == 0 or nb >= N * bpr) and (n2 % groups == 0 or n2 >= N * groups))
+
+
+def module(w, N, K):
+    qs = SimpleNamespace(absmax=w[1], state2=SimpleNamespace(absmax=w[2]), dtype=torch.bfloat16)
+    return SimpleNamespace(weight=SimpleNamespace(data=w[0].view(-1, 1), quant_state=qs), out_features=N,
+                           in_features=K)
+
+
+def case(name, out):
+    route, M, K, Ns = CASES[name]
+    calls, reps = ARGS.calls, ARGS.bursts
+    ws_t = [weight(N, K) for N in Ns]
+    x = torch.randn(M, K, generator=g).to(torch.bfloat16).to(dev)
+    ys = [torch.empty(M, N, dtype=torch.bfloat16, device=dev) for N in Ns]
+    mats = (_lib.GemmMat * len(Ns))(*[_lib.GemmMat(w[0].data_ptr(), w[0].numel(), w[1].data_ptr(), w[1].numel(),
+                                                   w[2].data_ptr(), w[2].numel(), y.data_ptr(), N)
+                                      for w, y, N in zip(ws_t, ys, Ns)])
+    mods = [module(w, N, K) for w, N in zip(ws_t, Ns)]
+    st = torch.cuda.current_stream().cuda_stream
+    times = {k: [] for k in LIBS}
+    outs = {}
+    for rep in range(reps + 1):
+        order = list(LIBS) if rep % 2 == 0 else list(LIBS)[::-1]
+        for k in order:
+            L = LIBS[k]
+            if len(Ns) == 1:
+                wsz = L.nf4_gemm_workspace_bytes(M, Ns[0], K)
+            else:
+                wsz = L.nf4_gemm_grouped_workspace_bytes(M, K, mats, len(Ns), None)
+            ws = torch.zeros(max(wsz, 16), dtype=torch.uint8, device=dev)
+            w0 = ws_t[0]
+            _lib._lib = L  # the py route reads it on every call
+            last = None
+            torch.cuda.synchronize()
+            rcs = 0
+            t0 = time.perf_counter()
+            if route == "py" and len(Ns) == 1:
+                for _ in range(calls):
+                    last = P.nf4_linear(x, mods[0])
+            elif route == "py":
+                for _ in range(calls):
+                    last = P.nf4_linear_grouped(x, mods)
+            elif len(Ns) == 1:
+                f = L.nf4_gemm_ref
+                a = (x.data_ptr(), M, w0[0].data_ptr(), w0[0].numel(), w0[1].data_ptr(), w0[1].numel(),
+                     w0[2].data_ptr(), w0[2].numel(), ys[0].data_ptr(), _lib.BF16, Ns[0], K, ws.data_ptr(), wsz, st)
+                for _ in range(calls):
+                    rcs |= f(*a)
+            else:
+                f = L.nf4_gemm_ref_grouped
+                a = (x.data_ptr(), M, K, mats, len(Ns), _lib.BF16, ws.data_ptr(), wsz, None, st)
+                for _ in range(calls):
+                    rcs |= f(*a)
+            t1 = time.perf_counter()
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            assert rcs == 0, rcs
+            res = ys if route == "abi" else (last if isinstance(last, list) else [last])
+            outs.setdefault(k, [y.clone() for y in res])
+            if rep:  # the first round warms up
+                times[k].append({"host_us": (t1 - t0) / calls * 1e6, "drained_us": (t2 - t0) / calls * 1e6})
+    rec = {"case": name, "route": route, "M": M, "K": K, "Ns": list(Ns), "calls_per_burst": calls, "bursts": reps,
+           "wraps": any(wraps(N, K, w[1].numel(), w[2].numel()) for w, N in zip(ws_t, Ns))}
+    if "parent" in outs:
+        rec["outputs_bit_identical"] = all(torch.equal(a.view(torch.int16), b.view(torch.int16))
+                                           for a, b in zip(outs["parent"], outs["new"]))
+    for k in LIBS:
+        h = [t["host_us"] for t in times[k]]
+        d = [t["drained_us"] for t in times[k]]
+        rec[k] = {"host_us_median": round(statistics.median(h), 3), "host_us_min": round(min(h), 3),
+                  "host_us_max": round(max(h), 3), "drained_us_median": round(statistics.median(d), 3),
+                  "host_us": [round(v, 3) for v in h]}
+    if "parent" in rec:
+        p = rec["parent"]
+        rec["new_median_within_parent_spread"] = p["host_us_min"] <= rec["new"]["host_us_median"] <= p["host_us_max"]
+    print(json.dumps(rec), flush=True)
+    out.write(json.dumps(rec) + "\n")
+    out.flush()
+
+
+with open(ARGS.out, "w") as out:
+    for name in (CASES if ARGS.case == "all" else [ARGS.case]):
+        case(name, out)
