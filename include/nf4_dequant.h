@@ -293,6 +293,43 @@ int nf4_gemm_ref_grouped(const void* x, int64_t M, int64_t K, const nf4_gemm_mat
                          int32_t out_dtype, void* workspace, size_t workspace_bytes,
                          const nf4_gemm_cfg* cfg, void* hip_stream);
 
+/* The fused GEMM in bitsandbytes semantics: y = x . W^T for the weight nf4_quant_bnb* /
+ * bitsandbytes produce, a flat stream of N*K codes (row-major [N][K]) with one statistics
+ * block per `blocksize` elements.  Element (r, c) lies in 64-block f = r * (K / 64) + c / 64
+ * and statistics block i = f >> log2(blocksize / 64); its scale is
+ *   nf4_gemm_bnb:         s = fl32(fl32(code2[absmax_q[i]] * absmax2[i / blocksize2]) + offset)
+ *                         (two fp32 roundings, never a fused multiply-add)
+ *   nf4_gemm_bnb_single:  s = absmax[i]
+ * and W[r][c] = RNE16(fl32(NF4[code(r, c)] * s)), high nibble = even column: exactly the
+ * values nf4_dequant_bnb / nf4_dequant_bnb_single write, bit for bit; fp32 accumulation and
+ * one final rounding to out_dtype (fp16 / bf16).  Statistics never wrap around in this mode.
+ * `code2`: 256 fp32 on the device.  `offset`: ONE fp32 ON THE DEVICE, read by the kernel
+ * (no host copy, no synchronisation; it may change between calls); NULL = 0.
+ * Shape rules as nf4_gemm_ref (M <= NF4DQ_GEMM_MAX_M, N % 64 == 0, K % 128 == 0, packed_len
+ * == N*K/2; else NF4DQ_ERR_SHAPE).  blocksize: a power of two, 64..4096; blocksize2: a power
+ * of two >= 4 (else NF4DQ_ERR_ARG).  nb / nabs >= ceil(N*K / blocksize) and n2 >= ceil(that /
+ * blocksize2), else NF4DQ_ERR_SHAPE.  A null code2 / absmax2 / absmax_q: NF4DQ_ERR_ARG.
+ * M == 0 or N == 0: NF4DQ_OK, nothing launched.
+ * cfg NULL = the library's choice: what nf4_gemm_ref runs for (M, N, K) -- same kernel, same
+ * decomposition -- where that kernel has the mode, else the 128-deep kernel.  A cfg may
+ * name NF4DQ_GEMM_K128, _PERSIST, _XR or _GEMV (their rules above); with blocksize > 64
+ * only NF4DQ_GEMM_K128.  NF4DQ_GEMM_STREAM and NF4DQ_GEMM_XS do not have the mode:
+ * NF4DQ_ERR_ARG, as for any invalid cfg.
+ * Workspace (nf4_gemm_bnb_workspace_bytes; with cfg NULL enough for any blocksize), its
+ * zero-fill contract, the split-K error word and nf4_gemm_check_workspace: exactly as for
+ * nf4_gemm_ref.  Asynchronous on `hip_stream`; allocates nothing. */
+size_t nf4_gemm_bnb_workspace_bytes(int64_t M, int64_t N, int64_t K, const nf4_gemm_cfg* cfg);
+int nf4_gemm_bnb(const void* x, int64_t M, const uint8_t* packed, int64_t packed_len,
+                 const uint8_t* absmax_q, int64_t nb, const float* code2,
+                 const float* absmax2, int64_t n2, const float* offset,
+                 int32_t blocksize, int32_t blocksize2,
+                 void* y, int32_t out_dtype, int64_t N, int64_t K,
+                 void* workspace, size_t workspace_bytes, const nf4_gemm_cfg* cfg, void* hip_stream);
+int nf4_gemm_bnb_single(const void* x, int64_t M, const uint8_t* packed, int64_t packed_len,
+                        const float* absmax, int64_t nabs, int32_t blocksize,
+                        void* y, int32_t out_dtype, int64_t N, int64_t K,
+                        void* workspace, size_t workspace_bytes, const nf4_gemm_cfg* cfg, void* hip_stream);
+
 /* The split-K hand-off never hangs: a reducer that has polled a partner slice's
  * entries 2^16 times without seeing them gives up, reads them as NaN and sets a
  * sticky error word in the workspace header.  This call waits for `hip_stream`,

@@ -121,6 +121,11 @@ SIGNATURES = {
                                                            ctypes.POINTER(GemmCfg)]),
     "nf4_gemm_ref_grouped": (ctypes.c_int, [_P, _I64, _I64, ctypes.POINTER(GemmMat), _I32, _I32, _P, ctypes.c_size_t,
                                             ctypes.POINTER(GemmCfg), _P]),
+    "nf4_gemm_bnb_workspace_bytes": (ctypes.c_size_t, [_I64, _I64, _I64, ctypes.POINTER(GemmCfg)]),
+    "nf4_gemm_bnb": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _P, _I32, _I32, _P, _I32, _I64, _I64,
+                                    _P, ctypes.c_size_t, ctypes.POINTER(GemmCfg), _P]),
+    "nf4_gemm_bnb_single": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _I32, _P, _I32, _I64, _I64, _P,
+                                           ctypes.c_size_t, ctypes.POINTER(GemmCfg), _P]),
     "nf4_gemm_check_workspace": (ctypes.c_int, [_P, ctypes.c_size_t, _P]),
     "nf4_strerror": (ctypes.c_char_p, [ctypes.c_int]),
     "nf4_version": (ctypes.c_char_p, []),

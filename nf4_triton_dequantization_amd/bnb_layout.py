@@ -233,10 +233,12 @@ class Linear4bit(nn.Module):
         return self
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        from .kernel import dequantize_nf4_bnb
+        """``x @ W.t() + bias`` with W = ``dequantize_nf4_bnb(self)`` (``kernel.nf4_linear_bnb``).
+        Decode-shaped inputs (at most 32 rows, N % 64 == 0, K % 128 == 0, no gradient recorded
+        for ``x``) run one fused dequant + GEMM launch with no host synchronisation; anything
+        else dequantizes and multiplies with torch, as every input did before.  The weights
+        are the same bit for bit and both accumulate in fp32; the last bit of ``y`` may differ
+        between the two paths (summation order), as documented for ``nf4_linear``."""
+        from .kernel import nf4_linear_bnb
 
-        w = dequantize_nf4_bnb(self)
-        y = x.to(w.dtype) @ w.t()
-        if self.bias is not None:
-            y = y + self.bias.to(y.dtype)
-        return y
+        return nf4_linear_bnb(x, self, self.bias)

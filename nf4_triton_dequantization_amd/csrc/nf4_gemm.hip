@@ -11,6 +11,16 @@ using namespace nf4gemm;
 
 int launch(const nf4_gemm_cfg& cfg, const HostMat* h, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
            void* workspace, int cus, hipStream_t st) {
+    if (count > 0 && h[0].mode != kScaleRef) {  // bitsandbytes scale modes: one weight, a family that has them
+        if (count != 1 || !bnb_cfg_ok(cfg, h[0])) return NF4DQ_ERR_ARG;
+        switch (cfg.kernel) {
+            case NF4DQ_GEMM_K128: return launch_k128_bnb(h, count, x, M, K, dtype, cfg, workspace, cus, st);
+            case NF4DQ_GEMM_PERSIST: return launch_persist_bnb(h, count, x, M, K, dtype, cfg, workspace, cus, st);
+            case NF4DQ_GEMM_XR: return launch_xr_bnb(h, count, x, M, K, dtype, cfg, workspace, cus, st);
+            case NF4DQ_GEMM_GEMV: return launch_gemv_bnb(h, count, x, M, K, dtype, cfg, workspace, cus, st);
+        }
+        return NF4DQ_ERR_ARG;
+    }
     switch (cfg.kernel) {
         case NF4DQ_GEMM_K128: return launch_k128(h, count, x, M, K, dtype, cfg, workspace, cus, st);
         case NF4DQ_GEMM_STREAM: return launch_stream(h, count, x, M, K, dtype, cfg, workspace, cus, st);
@@ -62,6 +72,39 @@ int gemm_impl(const void* x, int64_t M, const uint8_t* packed, int64_t packed_le
     const int cus = device_cus();
     const Choice ch = cfgp ? explicit_choice(*cfgp, M, N, K) : library_choice(M, K, &h, 1, cus);
     if (!valid_gemm_cfg(ch.first, M, N, K)) return NF4DQ_ERR_ARG;
+    return run(ch, cfgp != nullptr, cus, &h, 1, N, x, M, K, dtype, workspace, workspace_bytes, st);
+}
+
+// bitsandbytes semantics (nf4_gemm_bnb, nf4_gemm_bnb_single): the flat stream's statistics,
+// no wrap.  Single mode: absmax_q and code2 null, absmax2 = the fp32 absmax, n2 = its length.
+int gemm_bnb_impl(bool single, const void* x, int64_t M, const uint8_t* packed, int64_t packed_len,
+                  const uint8_t* absmax_q, int64_t nb, const float* code2, const float* absmax2, int64_t n2,
+                  const float* offset, int32_t blocksize, int32_t blocksize2, void* y, int32_t dtype, int64_t N,
+                  int64_t K, void* workspace, size_t workspace_bytes, const nf4_gemm_cfg* cfgp, hipStream_t st) {
+    if (dtype != NF4DQ_F16 && dtype != NF4DQ_BF16) return NF4DQ_ERR_ARG;
+    if (M < 0 || N < 0 || K < 0 || nb < 0 || n2 < 0) return NF4DQ_ERR_ARG;
+    if (blocksize < 64 || blocksize > 4096 || (blocksize & (blocksize - 1))) return NF4DQ_ERR_ARG;
+    if (!single && (blocksize2 < 4 || (blocksize2 & (blocksize2 - 1)))) return NF4DQ_ERR_ARG;
+    if (M == 0 || N == 0) return NF4DQ_OK;
+    if (!x || !packed || !absmax2 || !y || (!single && (!absmax_q || !code2))) return NF4DQ_ERR_ARG;
+    if (M > NF4DQ_GEMM_MAX_M || N % 64 || K % kChunkK || packed_len != N * (K / 2)) return NF4DQ_ERR_SHAPE;
+    if ((size_t)(N / 16) * 4 > kCounterBytes) return NF4DQ_ERR_TOO_LARGE;
+    if (packed_len >= (int64_t(1) << 31) || M * K * 2 >= (int64_t(1) << 31)) return NF4DQ_ERR_TOO_LARGE;
+    int sh = 0, sh2 = 0;
+    while ((64 << sh) < blocksize) ++sh;
+    while (!single && (1 << sh2) < blocksize2) ++sh2;
+    const int64_t nblk = (N * K + blocksize - 1) / blocksize;
+    if (single ? n2 < nblk : (nb < nblk || n2 < (nblk + blocksize2 - 1) / blocksize2)) return NF4DQ_ERR_SHAPE;
+    HostMat h{packed, packed_len, absmax_q, single ? n2 : nb, absmax2, n2, y, N};
+    h.mode = single ? kScaleBnbSingle : kScaleBnb;
+    h.code2 = code2;
+    h.offset = single ? nullptr : offset;
+    h.sh = sh;
+    h.sh2 = sh2;
+    const int cus = device_cus();
+    const Choice ch = cfgp ? explicit_choice(*cfgp, M, N, K) : bnb_choice(M, K, h, cus);
+    // a family without the mode (or, above blocksize 64, any but the 128-deep one) is the caller's error
+    if (!bnb_cfg_ok(ch.first, h) || !valid_gemm_cfg(ch.first, M, N, K)) return NF4DQ_ERR_ARG;
     return run(ch, cfgp != nullptr, cus, &h, 1, N, x, M, K, dtype, workspace, workspace_bytes, st);
 }
 
@@ -119,6 +162,26 @@ int nf4_gemm_ref(const void* x, int64_t M, const uint8_t* packed, int64_t packed
 size_t nf4_gemm_grouped_workspace_bytes(int64_t M, int64_t K, const nf4_gemm_mat* mats, int32_t count,
                                         const nf4_gemm_cfg* cfg) {
     return grouped_workspace(M, K, mats, count, cfg);
+}
+
+size_t nf4_gemm_bnb_workspace_bytes(int64_t M, int64_t N, int64_t K, const nf4_gemm_cfg* cfg) {
+    return cfg ? workspace_need(M, N, K, *cfg) : bnb_library_workspace(M, N, K);
+}
+
+int nf4_gemm_bnb(const void* x, int64_t M, const uint8_t* packed, int64_t packed_len, const uint8_t* absmax_q,
+                 int64_t nb, const float* code2, const float* absmax2, int64_t n2, const float* offset,
+                 int32_t blocksize, int32_t blocksize2, void* y, int32_t out_dtype, int64_t N, int64_t K,
+                 void* workspace, size_t workspace_bytes, const nf4_gemm_cfg* cfg, void* hip_stream) {
+    return gemm_bnb_impl(false, x, M, packed, packed_len, absmax_q, nb, code2, absmax2, n2, offset, blocksize,
+                         blocksize2, y, out_dtype, N, K, workspace, workspace_bytes, cfg,
+                         reinterpret_cast<hipStream_t>(hip_stream));
+}
+
+int nf4_gemm_bnb_single(const void* x, int64_t M, const uint8_t* packed, int64_t packed_len, const float* absmax,
+                        int64_t nabs, int32_t blocksize, void* y, int32_t out_dtype, int64_t N, int64_t K,
+                        void* workspace, size_t workspace_bytes, const nf4_gemm_cfg* cfg, void* hip_stream) {
+    return gemm_bnb_impl(true, x, M, packed, packed_len, nullptr, 0, nullptr, absmax, nabs, nullptr, blocksize, 1, y,
+                         out_dtype, N, K, workspace, workspace_bytes, cfg, reinterpret_cast<hipStream_t>(hip_stream));
 }
 
 int nf4_gemm_ref_grouped(const void* x, int64_t M, int64_t K, const nf4_gemm_mat* mats, int32_t count,

@@ -340,7 +340,41 @@ struct GemmArgs {
     uint32_t chunks;        // K / 128
     uint32_t bpr, groups;   // K / 64, ceil(bpr / 4)
     uint32_t per_wg;        // register-resident kernel: strips per workgroup
+    // bitsandbytes scale modes (SM != kScaleRef; one weight per launch): see block_scale
+    const float* code2;     // [256]
+    const float* offset;    // [1] or null (= 0)
+    uint32_t sh, sh2;       // log2(blocksize / 64), log2(blocksize2)
 };
+
+// The scale modes (nf4_gemm_plan.h).  In the bnb modes a 64-block is numbered on the flat
+// stream, f = row * bpr + block of the row, its statistics block is i = f >> sh, and
+//   nested:  s = fl32(fl32(code2[a1[i]] * a2[i >> sh2]) + offset)   (two roundings; the
+//            project builds with -ffp-contract=off, as nf4_dequant_bnb's kernels rely on)
+//   single:  s = a2[i]
+// -- the scales nf4_dequant_bnb / nf4_dequant_bnb_single apply, so the weights entering the
+// MFMAs are theirs bit for bit.  `tab` is the kernel's 256-entry LDS table: q / 127 in the
+// reference mode, code2 in the nested one.
+template <int SM>
+__device__ __forceinline__ float block_scale(const float* tab, uint32_t qa, float qb, float off) {
+    if constexpr (SM == kScaleBnb) return tab[qa] * qb + off;
+    else if constexpr (SM == kScaleBnbSingle) return qb;
+    else return tab[qa] * qb;  // (:45, :97-98)
+}
+
+// The launch's offset: one wave-uniform load (a null pointer means 0).
+template <int SM>
+__device__ __forceinline__ float load_offset(const float* offset) {
+    if constexpr (SM == kScaleBnb) return offset ? *offset : 0.0f;
+    else return 0.0f;
+}
+
+// A thread's entry of the code2 table, loaded ahead of everything else so that the wait
+// before its LDS store (ahead of the kernels' first barrier) is on the oldest load.
+template <int SM>
+__device__ __forceinline__ float load_code2(const float* code2) {
+    if constexpr (SM == kScaleBnb) return code2[threadIdx.x & 255u];
+    else return 0.0f;
+}
 
 // One 128-deep K chunk of one lane: for each of the wave's NT 16-column strips,
 // 16 packed weight bytes of its row there (one 64-block, so one scale), and
@@ -355,7 +389,7 @@ struct Chunk {
 };
 
 // VS: the block scales come from the workgroup's LDS table (nf4_gemm_smallm_kernel), no per-chunk gathers
-template <int MT, int NT, bool VS>
+template <int MT, int NT, bool VS, int SM>
 __device__ __forceinline__ void chunk_issue(const GemmArgs& A, const K128Mat& Mt, __amdgpu_buffer_rsrc_t rw,
                                             __amdgpu_buffer_rsrc_t rx, uint32_t c, bool valid, uint32_t row,
                                             uint32_t nl, uint32_t kh, Chunk<MT, NT>& in) {
@@ -376,8 +410,14 @@ __device__ __forceinline__ void chunk_issue(const GemmArgs& A, const K128Mat& Mt
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const uint32_t r = row + 16u * nt;
-            in.qa[nt] = Mt.a1[fmodu(r * A.bpr + b, Mt.nb)];             // (:173-177 wrap)
-            in.qb[nt] = Mt.a2[fmodu(r * A.groups + (b >> 2), Mt.n2)];  // (:40-41, :183-186 wrap)
+            if constexpr (SM == kScaleRef) {
+                in.qa[nt] = Mt.a1[fmodu(r * A.bpr + b, Mt.nb)];             // (:173-177 wrap)
+                in.qb[nt] = Mt.a2[fmodu(r * A.groups + (b >> 2), Mt.n2)];  // (:40-41, :183-186 wrap)
+            } else {
+                const uint32_t i = (r * A.bpr + b) >> A.sh;  // statistics block on the flat stream
+                if constexpr (SM == kScaleBnb) in.qa[nt] = Mt.a1[i];
+                in.qb[nt] = Mt.a2[SM == kScaleBnb ? i >> A.sh2 : i];
+            }
         }
     }
 }
@@ -420,10 +460,13 @@ __device__ __forceinline__ void chunk_mma(const Chunk<MT, NT>& in, const float* 
 // Workgroup = WV waves owning 16 NT output columns (NT strips) of one K slice;
 // wave w takes every WV-th group of D chunks, D chunks in flight at a time; the
 // waves' partial sums are combined through LDS (fixed order, one strip at a time).
-template <int DT, int MT, int D, int WV, int NT, bool VS>
+template <int DT, int MT, int D, int WV, int NT, bool VS, int SM = kScaleRef>
 __global__ __launch_bounds__(64 * WV) void nf4_gemm_smallm_kernel(const GemmArgs A) {
     constexpr int kGemmWaves = WV;
     __shared__ __attribute__((aligned(16))) float lut[20];  // 16 codes + the last-arriver flag
+    __shared__ float c2tab[SM == kScaleBnb && !VS ? 256 : 1];  // nested mode, gathered scales: code2
+    const float c2v = VS ? 0.0f : load_code2<SM>(A.code2);
+    const float off = load_offset<SM>(A.offset);
     __shared__ __attribute__((aligned(16))) f32x4 red[WV][MT][64];
     extern __shared__ __attribute__((aligned(16))) float scl[];  // VS: [16 NT rows][2 chunks_per_split blocks]
     const uint32_t lane = threadIdx.x & 63u;
@@ -456,9 +499,11 @@ __global__ __launch_bounds__(64 * WV) void nf4_gemm_smallm_kernel(const GemmArgs
     for (uint32_t g = c0 + wave * D; g < c1 || first; g += kGemmWaves * D) {
         Chunk<MT, NT> ch[D];
 #pragma unroll
-        for (int d = 0; d < D; ++d) chunk_issue<MT, NT, VS>(A, Mt, rw, rx, g + d, g + d < c1, row, nl, kh, ch[d]);
+        for (int d = 0; d < D; ++d) chunk_issue<MT, NT, VS, SM>(A, Mt, rw, rx, g + d, g + d < c1, row, nl, kh, ch[d]);
         if (first) {  // LUT (+ VS: the slice's scale table) and the barrier overlap the first loads
             write_lut(lut);
+            if constexpr (SM == kScaleBnb && !VS)
+                if (threadIdx.x < 256u) c2tab[threadIdx.x] = c2v;
             if constexpr (VS) {
                 // the workgroup's 16 NT rows x this slice's blocks: coalesced byte / float
                 // loads (consecutive threads, consecutive blocks of a row), one IEEE
@@ -468,8 +513,15 @@ __global__ __launch_bounds__(64 * WV) void nf4_gemm_smallm_kernel(const GemmArgs
                     const uint32_t rr = i / nbs, j = i - rr * nbs;
                     if (j < nbl) {
                         const uint32_t r = r0 + rr, gb = b0 + j;  // no wrap inside a row (host-checked)
-                        const float q = (float)Mt.a1[fmodu(r * A.bpr, Mt.nb) + gb];
-                        scl[i] = (q / 127.0f) * Mt.a2[fmodu(r * A.groups, Mt.n2) + (gb >> 2)];
+                        if constexpr (SM == kScaleRef) {
+                            const float q = (float)Mt.a1[fmodu(r * A.bpr, Mt.nb) + gb];
+                            scl[i] = (q / 127.0f) * Mt.a2[fmodu(r * A.groups, Mt.n2) + (gb >> 2)];
+                        } else {
+                            // once per block and launch: code2 straight from memory (block_scale)
+                            const uint32_t sb = (r * A.bpr + gb) >> A.sh;
+                            if constexpr (SM == kScaleBnb) scl[i] = A.code2[Mt.a1[sb]] * Mt.a2[sb >> A.sh2] + off;
+                            else scl[i] = Mt.a2[sb];
+                        }
                     }
                 }
             }
@@ -484,8 +536,10 @@ __global__ __launch_bounds__(64 * WV) void nf4_gemm_smallm_kernel(const GemmArgs
                 if constexpr (VS) {
                     const uint32_t j = 2u * (g + d - c0) + (kh >> 1);
                     scs[nt] = g + d < c1 ? scl[(16u * nt + nl) * nbs + j] : 0.0f;
-                } else {
+                } else if constexpr (SM == kScaleRef) {
                     scs[nt] = ((float)ch[d].qa[nt] / 127.0f) * ch[d].qb[nt];  // IEEE division, fp32 multiply (:45)
+                } else {
+                    scs[nt] = block_scale<SM>(c2tab, ch[d].qa[nt], ch[d].qb[nt], off);
                 }
             }
             chunk_mma<DT, MT, NT>(ch[d], lut, scs, acc);
@@ -770,7 +824,7 @@ __device__ __forceinline__ void xmat_load(const GemmArgs& A, uint32_t strip, XMa
     m.next = mi + 1u < A.nmat ? A.mat[mi + 1u].cg_begin : 0xFFFFFFFFu;
 }
 
-template <int KPW>
+template <int KPW, int SM>
 __device__ __forceinline__ void xslot_issue(const GemmArgs& A, uint32_t strip, bool valid, uint32_t cw,
                                             const XLane& ln, XMat& Mt, XSlot<KPW>& s) {
     if (strip >= Mt.next) xmat_load(A, strip, Mt);  // uniform; scalar loads only
@@ -790,9 +844,15 @@ __device__ __forceinline__ void xslot_issue(const GemmArgs& A, uint32_t strip, b
 #pragma unroll
         for (int q = 0; q < WQ; ++q)
             s.w[WQ * h + q] = NF4_ABL_WLOAD(rw, (w0 + 16u * q) | oob);
-        s.qa[h] = (uint8_t)NF4_ABL_SLOAD(ra1, fmodu(r0 * A.bpr + 2u * c + ln.b1, Mt.nb) | oob, true);  // (:173-177)
-        s.qb[h] = __uint_as_float(
-            NF4_ABL_SLOAD(ra2, (fmodu(r0 * A.groups + (c >> 1) + ln.b2, Mt.n2) * 4u) | oob, false));  // (:40-41, :183-186)
+        if constexpr (SM == kScaleRef) {
+            s.qa[h] = (uint8_t)NF4_ABL_SLOAD(ra1, fmodu(r0 * A.bpr + 2u * c + ln.b1, Mt.nb) | oob, true);  // (:173-177)
+            s.qb[h] = __uint_as_float(
+                NF4_ABL_SLOAD(ra2, (fmodu(r0 * A.groups + (c >> 1) + ln.b2, Mt.n2) * 4u) | oob, false));  // (:40-41, :183-186)
+        } else {
+            const uint32_t f = r0 * A.bpr + 2u * c + ln.b1;  // the lane's 64-block on the flat stream (sh = 0)
+            if constexpr (SM == kScaleBnb) s.qa[h] = (uint8_t)NF4_ABL_SLOAD(ra1, f | oob, true);
+            s.qb[h] = __uint_as_float(NF4_ABL_SLOAD(ra2, ((SM == kScaleBnb ? f >> A.sh2 : f) * 4u) | oob, false));
+        }
     }
 }
 
@@ -867,14 +927,17 @@ __device__ __forceinline__ void xr_pair_mma(const u32x4& w0, const u32x4& w1, fl
 // 4-11 of the next) the 16 lanes then hit 16 distinct 4-bank sets.
 __device__ __forceinline__ uint32_t xr_xsw(uint32_t r) { return r ^ ((((r + 4u) >> 3) & 1u) << 3); }
 
-template <int DT, int MT, int WV, int KPW, int D, int GU>
+template <int DT, int MT, int WV, int KPW, int D, int GU, int SM>
 __device__ __forceinline__ void xr_body(const GemmArgs& A) {
     extern __shared__ __attribute__((aligned(16))) f32x4 xr_smem[];  // dynamic part (host: xr_lds_dynamic)
     // 256-deep chunks: the pair table (64 KiB) and the q/127 table, static so that the
     // lookups' addresses need no base added (one VALU per two weights less than in a
     // dynamic region, whose base the compiler adds as a late-resolved 0)
     __shared__ __attribute__((aligned(16))) f32x2 xr_ptab[KPW >= 2 ? 256 * 32 : 2];
-    __shared__ float xr_qtab[KPW >= 2 ? 256 : 4];
+    __shared__ float xr_qtab[KPW >= 2 || SM == kScaleBnb ? 256 : 4];  // q / 127, or code2 (nested mode)
+    static_assert(sizeof(xr_ptab) + sizeof(xr_qtab) <= xr_lds_static(KPW, SM), "the plan's static LDS covers the tables");
+    const float c2v = load_code2<SM>(A.code2);
+    const float off = load_offset<SM>(A.offset);
     f32x2* ptab = xr_ptab;
     float* qtab = xr_qtab;
     // partial tiles meet once per R strips (8 waves: two strips per barrier)
@@ -954,7 +1017,7 @@ __device__ __forceinline__ void xr_body(const GemmArgs& A) {
     xmat_load(A, s0, xm);
 #pragma unroll
     for (int d = 0; d < D; ++d) {
-        xslot_issue<KPW>(A, s0 + (uint32_t)d, (uint32_t)d < nst, cw, ln, xm, ring[d]);
+        xslot_issue<KPW, SM>(A, s0 + (uint32_t)d, (uint32_t)d < nst, cw, ln, xm, ring[d]);
         __builtin_amdgcn_sched_barrier(0);
     }
     NF4_GSTAMP(10);
@@ -962,7 +1025,9 @@ __device__ __forceinline__ void xr_body(const GemmArgs& A) {
         // the x DMA went out before the ring's D x 4 loads: wait for it alone (the
         // compiler does not order LDS-DMA writes before these LDS reads by itself);
         // an ablation build whose ring issues fewer loads waits for everything
-        if constexpr (NF4_ABL_RING_FULL) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * D) : "memory");
+        // (a ring slot: two weight loads and the statistic gathers, one in single mode)
+        constexpr int kSlotLoads = SM == kScaleBnbSingle ? 3 : 4;
+        if constexpr (NF4_ABL_RING_FULL) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kSlotLoads * D) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         // fragment (q, s) of row tile mt = piece 8 kh + 4 q + s of row 16 mt + nl
 #pragma unroll
@@ -978,8 +1043,11 @@ __device__ __forceinline__ void xr_body(const GemmArgs& A) {
         __syncthreads();  // every wave's fragments out of the pair table's region before the tables
     }
     write_lut(lut);
+    if constexpr (SM == kScaleBnb)
+        if (tid < 256u) qtab[tid] = c2v;
     if constexpr (KPW >= 2) {  // tables while the loads fly (as the streaming kernels)
-        if (tid < 256u) qtab[tid] = (float)tid / 127.0f;  // IEEE division (:45)
+        if constexpr (SM == kScaleRef)
+            if (tid < 256u) qtab[tid] = (float)tid / 127.0f;  // IEEE division (:45)
         for (uint32_t u = tid; u < 16u * 32u; u += 64u * WV) {
             const float clo = nf4_code(u >> 5);
 #pragma unroll
@@ -1022,7 +1090,8 @@ __device__ __forceinline__ void xr_body(const GemmArgs& A) {
                     for (int h = 0; h < KPW / 2; ++h) {
                         const u32x4 (&xs)[2][MT][4] = *reinterpret_cast<const u32x4 (*)[2][MT][4]>(&xf[2 * h]);
                         xr_pair_mma<DT, MT>(ring[d].w[2 * h], ring[d].w[2 * h + 1],
-                                            qtab[ring[d].qa[h]] * ring[d].qb[h], ptab, slot8, xs, acc);
+                                            block_scale<SM>(qtab, ring[d].qa[h], ring[d].qb[h], off), ptab, slot8,
+                                            xs, acc);
                     }
                 }
                 if (t == 0) NF4_GSTAMP(2);  // x and the first strip's weights arrived, first strip done
@@ -1034,7 +1103,10 @@ __device__ __forceinline__ void xr_body(const GemmArgs& A) {
                     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                         for (int s = 0; s < 4; ++s) ch.x[mt][s] = xf[q][mt][s];
-                    const float scs[1] = {((float)ring[d].qa[q / 2] / 127.0f) * ring[d].qb[q / 2]};  // IEEE division (:45)
+                    float sc1;
+                    if constexpr (SM == kScaleRef) sc1 = ((float)ring[d].qa[q / 2] / 127.0f) * ring[d].qb[q / 2];  // IEEE division (:45)
+                    else sc1 = block_scale<SM>(qtab, ring[d].qa[q / 2], ring[d].qb[q / 2], off);
+                    const float scs[1] = {sc1};
                     f32x4 a1[MT][1];
 #pragma unroll
                     for (int mt = 0; mt < MT; ++mt) a1[mt][0] = acc[mt];
@@ -1044,7 +1116,7 @@ __device__ __forceinline__ void xr_body(const GemmArgs& A) {
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-            xslot_issue<KPW>(A, s0 + t + (uint32_t)D, t + (uint32_t)D < nst, cw, ln, xm, ring[d]);
+            xslot_issue<KPW, SM>(A, s0 + t + (uint32_t)D, t + (uint32_t)D < nst, cw, ln, xm, ring[d]);
             __builtin_amdgcn_sched_barrier(0);
             if (d % R != R - 1) continue;  // the group's partials meet after its last strip
             const uint32_t tg = t + 1u - (uint32_t)R;  // first strip of the group
@@ -1244,18 +1316,18 @@ __device__ __forceinline__ void xr_body(const GemmArgs& A) {
     NF4_GSTAMP(9);
 }
 
-template <int DT, int MT, int WV, int KPW, int D, int GU>
+template <int DT, int MT, int WV, int KPW, int D, int GU, int SM = kScaleRef>
 __global__ __launch_bounds__(64 * WV) void nf4_gemm_xr_kernel(const GemmArgs A) {
-    xr_body<DT, MT, WV, KPW, D, GU>(A);
+    xr_body<DT, MT, WV, KPW, D, GU, SM>(A);
 }
 // GU > 0: the unrolled groups keep 4 x 4 exchange results per lane live across the
 // loop; at one workgroup of 8 waves per CU (2 per SIMD) the kernel may use up to
 // 256 registers, and with the default budget the allocator moved those results
 // between registers (each move a full vmcnt(0) drain inside the ring)
-template <int DT, int MT, int WV, int KPW, int D, int GU>
+template <int DT, int MT, int WV, int KPW, int D, int GU, int SM = kScaleRef>
 __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(1, 2))) void nf4_gemm_xrg_kernel(
     const GemmArgs A) {
-    xr_body<DT, MT, WV, KPW, D, GU>(A);
+    xr_body<DT, MT, WV, KPW, D, GU, SM>(A);
 }
 
 // ---------------------------------------------------------------------------
@@ -1284,8 +1356,26 @@ struct StreamMat {
     FastDiv nb, n2;
 };
 
+// The bitsandbytes scale modes' launch-wide fields (block_scale).  Those launches take one
+// weight, so in StreamArgs they lie over the second weight's slot: the struct keeps its
+// size, and with it the kernel arguments the runtime appends (the grid size the persistent
+// kernel reads first) stay in a cache line the kernel loads anyway -- 24 bytes more moved
+// them to a line of their own and cost the reference-mode persistent launches 2-4 %
+// (profiles/gemm_bnb/).
+struct BnbFields {
+    const float* code2;     // [256]
+    const float* offset;    // [1] or null (= 0)
+    uint32_t sh, sh2;       // 0, log2(blocksize2)
+};
+
 struct StreamArgs {
-    StreamMat mat[kGroupMax];
+    union {
+        StreamMat mat[kGroupMax];
+        struct {
+            StreamMat first;  // = mat[0]
+            BnbFields f;
+        } bnb;              // SM != kScaleRef (nmat == 1)
+    };
     uint32_t nmat;
     uint32_t sg_total;      // strip groups over all weights
     uint32_t ncols;         // sum of N (split-K slab row length)
@@ -1304,6 +1394,7 @@ struct StreamArgs {
     uint32_t red_off;       // [W][MT][64] f32x4 partial sums (persistent: two sets)
     uint32_t out_off;       // persistent: finished outputs [group][strip][M][16] (16-bit)
 };
+static_assert(sizeof(BnbFields) <= sizeof(StreamMat), "the bnb fields fit the second weight's slot");
 
 struct SSlot {
     u32x4 w0, w1;
@@ -1666,11 +1757,13 @@ struct PGeo {  // where the ring issues: one strip of one weight
     uint32_t wbase;  // the lane's first weight byte of the slice: row K / 2 + kh 32 + chunk base 128
 };
 
-template <int DT, int W, int P, bool SPLIT>
+template <int DT, int W, int P, bool SPLIT, int SM = kScaleRef>
 __global__ __launch_bounds__(64 * W) void nf4_gemm_persist_kernel(const StreamArgs A) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ __attribute__((aligned(16))) f32x2 ptab[256 * 32];
-    __shared__ float qtab[256];
+    __shared__ float qtab[256];  // q / 127, or code2 (nested mode)
+    const float c2v = load_code2<SM>(A.bnb.f.code2);
+    const float off = load_offset<SM>(A.bnb.f.offset);
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t nl = lane & 15u, kh = lane >> 4;
@@ -1697,8 +1790,15 @@ __global__ __launch_bounds__(64 * W) void nf4_gemm_persist_kernel(const StreamAr
         g.rw = __builtin_amdgcn_make_buffer_rsrc((void*)Mt.packed, 0, Mt.N * (A.K >> 1), kRsrcFlags);
         g.ra1 = __builtin_amdgcn_make_buffer_rsrc((void*)Mt.a1, 0, Mt.nb_bytes, kRsrcFlags);
         g.ra2 = __builtin_amdgcn_make_buffer_rsrc((void*)Mt.a2, 0, Mt.n2_bytes, kRsrcFlags);
-        g.b1 = fmodu(g.row * A.bpr, Mt.nb) + 4u * (cbase + l0);  // reference wrap (:173-186), none inside a row
-        g.b2 = fmodu(g.row * A.groups, Mt.n2) + cbase + l0;
+        if constexpr (SM == kScaleRef) {
+            g.b1 = fmodu(g.row * A.bpr, Mt.nb) + 4u * (cbase + l0);  // reference wrap (:173-186), none inside a row
+            g.b2 = fmodu(g.row * A.groups, Mt.n2) + cbase + l0;
+        } else {
+            // the flat stream: the lane's row starts at 64-block row * bpr (a multiple of 4:
+            // K % 256 == 0), so a chunk is the four blocks 4 b2 .. 4 b2 + 3 of one nested group
+            g.b1 = g.row * A.bpr + 4u * (cbase + l0);
+            g.b2 = (g.row * A.bpr >> 2) + cbase + l0;
+        }
         g.wbase = g.row * (A.K >> 1) + (cbase + l0) * 128u + kh * 32u;
     };
     // issue pointer: group it2, round rr2 of it
@@ -1707,8 +1807,19 @@ __global__ __launch_bounds__(64 * W) void nf4_gemm_persist_kernel(const StreamAr
     geo(0, gi);
     auto issue_scales = [&](PScales<P>& sc, bool valid) {
         const uint32_t oob = valid ? 0u : kOob;
-        sc.a1 = pload<P>(gi.ra1, (gi.b1 + 4u * P * rr2) | oob);
-        sc.a2 = pload<P>(gi.ra2, ((gi.b2 + P * rr2) * 4u) | oob);
+        if constexpr (SM != kScaleBnbSingle) sc.a1 = pload<P>(gi.ra1, (gi.b1 + 4u * P * rr2) | oob);
+        if constexpr (SM == kScaleRef) {
+            sc.a2 = pload<P>(gi.ra2, ((gi.b2 + P * rr2) * 4u) | oob);
+        } else {
+            // one gather per chunk: its nested scale (blocksize2 >= 4: one per chunk), or in
+            // single mode the lane's own block scale
+#pragma unroll
+            for (int s = 0; s < P; ++s) {
+                const uint32_t q = gi.b2 + P * rr2 + (uint32_t)s;  // the chunk: blocks 4 q .. 4 q + 3
+                const uint32_t i = SM == kScaleBnb ? q >> (A.bnb.f.sh2 - 2u) : 4u * q + kh;
+                sc.a2[s] = __builtin_amdgcn_raw_buffer_load_b32(gi.ra2, (i * 4u) | oob, 0, 0);
+            }
+        }
     };
     auto issue_w = [&](SSlot& sl, int s, bool valid) {
         const uint32_t woff = (gi.wbase + (rr2 * P + (uint32_t)s) * 128u) | (valid ? 0u : kOob);
@@ -1748,7 +1859,7 @@ __global__ __launch_bounds__(64 * W) void nf4_gemm_persist_kernel(const StreamAr
     }
     advance();
     // 2. tables while the loads fly, then the x rows, one barrier
-    if (tid < 256u) qtab[tid] = (float)tid / 127.0f;
+    if (tid < 256u) qtab[tid] = SM == kScaleBnb ? c2v : (float)tid / 127.0f;
     if (tid < 8u) *reinterpret_cast<u32x4*>(smem + A.zero_off + 16u * tid) = u32x4{0u, 0u, 0u, 0u};
     for (uint32_t u = tid; u < 16u * 32u; u += 64u * W) {
         const float clo = nf4_code(u >> 5);
@@ -1767,6 +1878,11 @@ __global__ __launch_bounds__(64 * W) void nf4_gemm_persist_kernel(const StreamAr
     f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}}, accb[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
     uint32_t it = 0, rr = 0, buf = 0;
 
+    // the block scale of chunk s of a round for this lane's block (kh of the chunk's four)
+    auto pscale = [&](const PScales<P>& cur, int s) {
+        const uint32_t qa = SM == kScaleBnbSingle ? 0u : (cur.a1[s] >> (8u * kh)) & 0xFFu;
+        return block_scale<SM>(qtab, qa, __uint_as_float(cur.a2[s]), off);  // (:45, :97-98)
+    };
     auto round = [&](PScales<P>& cur, PScales<P>& nxt) {
         const bool more = it2 < mine;  // the issue pointer is one round ahead
         issue_scales(nxt, more);
@@ -1776,8 +1892,7 @@ __global__ __launch_bounds__(64 * W) void nf4_gemm_persist_kernel(const StreamAr
             for (int s = 0; s < P; s += 2) {
                 const uint32_t l = l0 + rr * P + (uint32_t)s;
                 const uint32_t xa = live ? xa0 + l * 512u : xa0, xb = live ? xa + 512u : xa0;
-                const float scA = qtab[(cur.a1[s] >> (8u * kh)) & 0xFFu] * __uint_as_float(cur.a2[s]);  // (:45, :97-98)
-                const float scB = qtab[(cur.a1[s + 1] >> (8u * kh)) & 0xFFu] * __uint_as_float(cur.a2[s + 1]);
+                const float scA = pscale(cur, s), scB = pscale(cur, s + 1);
                 sslot_mma_pair<DT>(ring[s], ring[s + 1], scA, scB, ptab, smem, slot8, xa, xb, acc[0], accb[0]);
                 if (it == 0 && rr == 0 && s == 0) NF4_GSTAMP(2);
                 __builtin_amdgcn_sched_barrier(0);
@@ -1792,7 +1907,7 @@ __global__ __launch_bounds__(64 * W) void nf4_gemm_persist_kernel(const StreamAr
             float scv[P];
 #pragma unroll
             for (int s = 0; s < P; ++s)
-                scv[s] = qtab[(cur.a1[s] >> (8u * kh)) & 0xFFu] * __uint_as_float(cur.a2[s]);  // (:45, :97-98)
+                scv[s] = pscale(cur, s);
 #pragma unroll
             for (int s = 0; s < P; ++s) {
                 const uint32_t l = l0 + rr * P + (uint32_t)s;

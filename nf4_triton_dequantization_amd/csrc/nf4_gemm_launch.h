@@ -25,8 +25,30 @@ int launch_k128(const HostMat* mats, int count, const void* x, int64_t M, int64_
                 const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st);
 int launch_gemv(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
                 const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st);
+// The same launchers with the bitsandbytes scale modes (mats[0].mode: kScaleBnb or
+// kScaleBnbSingle; one weight), for the families that have them (bnb_has_mode).  Each is its
+// family's launcher source compiled once more with NF4_GEMM_BNB defined
+// (nf4_gemm_launch_*_bnb.hip), so the modes' kernels build beside the reference ones.
+int launch_persist_bnb(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
+                       const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st);
+int launch_xr_bnb(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
+                  const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st);
+int launch_k128_bnb(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
+                    const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st);
+int launch_gemv_bnb(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
+                    const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st);
 
 }  // namespace nf4gemm
+
+// What a launcher source defines and instantiates: launch_<family> with the reference
+// scale mode, or launch_<family>_bnb with the two bitsandbytes modes.
+#ifdef NF4_GEMM_BNB
+#define NF4_GEMM_FN(name_) name_##_bnb
+#define NF4_GEMM_MODES nf4gemm::kScaleBnb, nf4gemm::kScaleBnbSingle
+#else
+#define NF4_GEMM_FN(name_) name_
+#define NF4_GEMM_MODES nf4gemm::kScaleRef
+#endif
 
 namespace {
 
@@ -62,6 +84,19 @@ inline void fill_common(Args& a, int count, const void* x, int64_t M, int64_t K,
     a.ksplit = (uint32_t)cfg.ksplit;
     a.bpr = (uint32_t)(K / 64);
     a.groups = (a.bpr + 3) / 4;
+}
+
+// The scale mode's launch-wide fields (the bnb entries take one weight).
+template <class Args>
+inline void fill_mode(Args& a, const HostMat& h) {
+    a.code2 = h.code2;
+    a.offset = h.offset;
+    a.sh = (uint32_t)h.sh;
+    a.sh2 = (uint32_t)h.sh2;
+}
+
+inline void fill_mode(StreamArgs& a, const HostMat& h) {  // over the unused second weight's slot
+    a.bnb.f = BnbFields{h.code2, h.offset, (uint32_t)h.sh, (uint32_t)h.sh2};
 }
 
 // One weight's pointers, N and absmax divisors.  The divisors are clamped, nb at 2^31

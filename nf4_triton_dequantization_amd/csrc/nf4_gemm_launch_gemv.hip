@@ -22,6 +22,9 @@
 // Scales: block b = 32 j + l / 2 of the row: a1[(row bpr) mod nb + b], a2[(row groups)
 // mod n2 + b / 4] (absmax not wrapping inside a row, as the persistent kernel assumes),
 // s = (a1 / 127) * a2 (IEEE; the q/127 table), as kernel_optimized.py:40-45, :97-98.
+// The bitsandbytes scale modes (SM, nf4_gemm_dev.h::block_scale; blocksize 64): block
+// f = row bpr + b of the flat stream, a1[f], a2[f >> sh2] and code2 in the table's place, or
+// the fp32 a2[f] alone.
 #include "nf4_gemm_launch.h"
 
 namespace {
@@ -46,6 +49,10 @@ struct GemvArgs {
     const void* x;          // [K]
     uint32_t K, J;          // J = K / 2048 pieces per row
     uint32_t bpr, groups;   // K / 64, ceil(bpr / 4)
+    // bitsandbytes scale modes (one weight per launch)
+    const float* code2;     // [256]
+    const float* offset;    // [1] or null (= 0)
+    uint32_t sh, sh2;       // 0, log2(blocksize2)
 };
 
 template <int R>
@@ -58,7 +65,7 @@ struct GvUnit {
 // One unit's loads: R rows x 16 packed bytes per lane, and each row's absmax byte and
 // nested scale for the lane's block.  Invalid (past the wave's last unit): offsets beyond
 // every buffer range, no traffic.
-template <int R>
+template <int R, int SM>
 __device__ __forceinline__ void gv_issue(const GemvArgs& A, __amdgpu_buffer_rsrc_t rw, __amdgpu_buffer_rsrc_t ra1,
                                          __amdgpu_buffer_rsrc_t ra2, uint32_t lr, uint32_t j, const uint32_t (&rb1)[R],
                                          const uint32_t (&rb2)[R], bool valid, uint32_t lane, GvUnit<R>& u) {
@@ -67,8 +74,10 @@ __device__ __forceinline__ void gv_issue(const GemvArgs& A, __amdgpu_buffer_rsrc
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         u.w[r] = __builtin_amdgcn_raw_buffer_load_b128(rw, ((lr + r) * (A.K >> 1) + 1024u * j + 16u * lane) | oob, 0, 0);
-        u.qa[r] = __builtin_amdgcn_raw_buffer_load_b8(ra1, (rb1[r] + b) | oob, 0, 0);
-        u.qb[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ra2, ((rb2[r] + (b >> 2)) * 4u) | oob, 0, 0));
+        if constexpr (SM != kScaleBnbSingle) u.qa[r] = __builtin_amdgcn_raw_buffer_load_b8(ra1, (rb1[r] + b) | oob, 0, 0);
+        // reference: the row's nested base + b / 4; bnb: the flat block (rb1 = row bpr, no wrap)
+        const uint32_t i2 = SM == kScaleRef ? rb2[r] + (b >> 2) : SM == kScaleBnb ? (rb1[r] + b) >> A.sh2 : rb1[r] + b;
+        u.qb[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ra2, (i2 * 4u) | oob, 0, 0));
     }
 }
 
@@ -83,13 +92,13 @@ __device__ __forceinline__ float gv_dot(uint32_t w2, uint32_t x2, float c) {
 
 // Dequantize one unit (exact weights: fp32 code x block scale, RNE) and dot it with the
 // lane's x fragments into acc[r] (two chains per row).
-template <int DT, int R>
-__device__ __forceinline__ void gv_body(const GvUnit<R>& u, const char* pt, const float* qtab, const u32x4 (&xf)[4],
-                                        uint32_t slot8, float (&acc)[R][2]) {
+template <int DT, int R, int SM>
+__device__ __forceinline__ void gv_body(const GvUnit<R>& u, const char* pt, const float* qtab, float off,
+                                        const u32x4 (&xf)[4], uint32_t slot8, float (&acc)[R][2]) {
     f32x2 sc2[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const float sc = qtab[u.qa[r]] * u.qb[r];  // (:45, :97-98)
+        const float sc = block_scale<SM>(qtab, SM == kScaleBnbSingle ? 0u : u.qa[r], u.qb[r], off);  // (:45, :97-98)
         sc2[r] = f32x2{sc, opaque(sc)};
     }
     // steps st = (row, dword): pair lookups run LA steps ahead of their use
@@ -129,11 +138,13 @@ __device__ __forceinline__ void gv_store(void* y, uint32_t i, float v) {
 
 // (Measured and not kept, profiles/r06/gemm/s30_gemv_ab.jsonl: x held in registers at
 // K = 4096 instead of LDS reads, 4 units in flight per wave instead of 2.)
-template <int DT, int W, int R>
+template <int DT, int W, int R, int SM = kScaleRef>
 __global__ __launch_bounds__(64 * W) void nf4_gemv_kernel(const GemvArgs A) {
     extern __shared__ __attribute__((aligned(16))) char xs[];        // x, swizzled (see top)
     __shared__ __attribute__((aligned(16))) f32x2 ptab[256 * 32];   // pair table, 32 lane slots
-    __shared__ float qtab[256];
+    __shared__ float qtab[256];                                     // q / 127, or code2 (nested mode)
+    const float c2v = load_code2<SM>(A.code2);
+    const float off = load_offset<SM>(A.offset);
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t nw = gridDim.x * W;
@@ -161,8 +172,8 @@ __global__ __launch_bounds__(64 * W) void nf4_gemv_kernel(const GemvArgs A) {
         const GemvMat& Mt = A.mat[m];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            rb1[r] = fmodu((lr + r) * A.bpr, Mt.nb);
-            rb2[r] = fmodu((lr + r) * A.groups, Mt.n2);
+            rb1[r] = SM == kScaleRef ? fmodu((lr + r) * A.bpr, Mt.nb) : (lr + r) * A.bpr;
+            rb2[r] = SM == kScaleRef ? fmodu((lr + r) * A.groups, Mt.n2) : 0u;
         }
     };
     __amdgpu_buffer_rsrc_t rw, r1, r2;
@@ -172,11 +183,11 @@ __global__ __launch_bounds__(64 * W) void nf4_gemv_kernel(const GemvArgs A) {
     row_bases(mi, lr, rb1, rb2);
     constexpr int D = 2;
     GvUnit<R> ring[D];
-    gv_issue<R>(A, rw, r1, r2, lr, 0u, rb1, rb2, g < A.groups_total, lane, ring[0]);
+    gv_issue<R, SM>(A, rw, r1, r2, lr, 0u, rb1, rb2, g < A.groups_total, lane, ring[0]);
 
     // tables: q / 127 (IEEE division, :45), the pair table (code[b >> 4], code[b & 15])
     // in 32 lane slots; then x into its swizzled layout
-    if (tid < 256u) qtab[tid] = (float)tid / 127.0f;
+    if (tid < 256u) qtab[tid] = SM == kScaleBnb ? c2v : (float)tid / 127.0f;
     for (uint32_t i = tid; i < 256u * 16u; i += 64u * W) {  // two slots per 16-byte write
         const uint32_t b = i >> 4;
         const float hi = nf4_code(b >> 4), lo = nf4_code(b & 15u);
@@ -245,7 +256,7 @@ __global__ __launch_bounds__(64 * W) void nf4_gemv_kernel(const GemvArgs A) {
     for (int r = 0; r < R; ++r) nb1[r] = rb1[r], nb2[r] = rb2[r];
     auto issue_next = [&](GvUnit<R>& u) {
         next_unit(ng, nj, nm, nl, nw_, n1, n2, nb1, nb2);
-        gv_issue<R>(A, nw_, n1, n2, nl, nj, nb1, nb2, ng < A.groups_total, lane, u);
+        gv_issue<R, SM>(A, nw_, n1, n2, nl, nj, nb1, nb2, ng < A.groups_total, lane, u);
     };
     auto advance_p = [&]() {
         if (++pj < A.J) return;
@@ -263,7 +274,7 @@ __global__ __launch_bounds__(64 * W) void nf4_gemv_kernel(const GemvArgs A) {
             if (!live) break;  // wave-uniform: every unit of the wave decoded
             issue_next(ring[(i + D - 1) % D]);
             const u32x4 xf[4] = {xfrag(pj, 0), xfrag(pj, 1), xfrag(pj, 2), xfrag(pj, 3)};
-            gv_body<DT, R>(ring[i], pt, qtab, xf, slot8, acc);
+            gv_body<DT, R, SM>(ring[i], pt, qtab, off, xf, slot8, acc);
             if (pj + 1 == A.J) finish(pm, pl);
             advance_p();
             live = pg < A.groups_total;
@@ -279,7 +290,7 @@ namespace nf4gemm {
 // inside a row).  cfg.waves: waves per workgroup (8 / 16); cfg.depth: rows per row group R
 // (1 / 2 / 4); cfg.strips: workgroups per CU in the grid (0 / 1 / 2, 0 = 1), at most one
 // row group per wave.
-int launch_gemv(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
+int NF4_GEMM_FN(launch_gemv)(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
                 const nf4_gemm_cfg& cfg, void*, int cus, hipStream_t st) {
     if (M != 1 || cfg_runs(cfg, M, K, mats, count, cus) != NF4DQ_OK) return NF4DQ_ERR_ARG;  // not a plan
     GemvArgs A{};
@@ -299,12 +310,15 @@ int launch_gemv(const HostMat* mats, int count, const void* x, int64_t M, int64_
         rows += m.N;
     }
     A.groups_total = rows / (uint32_t)cfg.depth;
+    if (count > 0) fill_mode(A, mats[0]);
     const LaunchShape ls = launch_shape(cfg, M, K, mats, count, cus);
     const dim3 grid(ls.grid), block(ls.block);
     pick<NF4DQ_BF16, NF4DQ_F16>(dtype, [&](auto DT) {
         pick<8, 16>(cfg.waves, [&](auto W) {
             pick<1, 2, 4>(cfg.depth, [&](auto R) {
-                launch_lds<&nf4_gemv_kernel<DT, W, R>>(65536, grid, block, ls.dyn, st, A);
+                pick<NF4_GEMM_MODES>(count > 0 ? mats[0].mode : kScaleRef, [&](auto SM) {
+                    launch_lds<&nf4_gemv_kernel<DT, W, R, SM>>(65536, grid, block, ls.dyn, st, A);
+                });
             });
         });
     });

@@ -6,7 +6,7 @@ namespace nf4gemm {
 
 // One launch of the 128-deep kernel over `count` weights sharing x (shapes and cfg
 // validated; an empty weight owns no column group).
-int launch_k128(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
+int NF4_GEMM_FN(launch_k128)(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
                 const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st) {
     const int nt = cfg.strips > 1 ? cfg.strips : 1;  // 16-column strips per wave
     GemmArgs A{};
@@ -24,6 +24,7 @@ int launch_k128(const HostMat* mats, int count, const void* x, int64_t M, int64_
     }
     A.col_groups = cgs;
     A.ncols = cols;
+    if (count > 0) fill_mode(A, mats[0]);
     const LaunchShape ls = launch_shape(cfg, M, K, mats, count, cus);
     const bool vs = ls.dyn != 0;  // the scale table in LDS: the vector-scale form
     const dim3 grid(ls.grid), block(ls.block);
@@ -34,11 +35,13 @@ int launch_k128(const HostMat* mats, int count, const void* x, int64_t M, int64_
                 if constexpr (MT == 1 || D != 4)  // two row tiles: at most 2 chunks in flight
                     pick<8, 4>(cfg.waves, [&](auto W) {
                         pick<4, 2, 1>(nt, [&](auto NT) {
-                            constexpr auto scales_in_lds = &nf4_gemm_smallm_kernel<DT, MT, D, W, NT, true>;
-                            constexpr auto scales_gathered = &nf4_gemm_smallm_kernel<DT, MT, D, W, NT, false>;
-                            if (vs) hipLaunchKernelGGL(scales_in_lds, grid, block, ls.dyn, st, A);
-                            else hipLaunchKernelGGL(scales_gathered, grid, block, 0, st, A);
-                            rc = hip_rc2(hipGetLastError());
+                            pick<NF4_GEMM_MODES>(count > 0 ? mats[0].mode : kScaleRef, [&](auto SM) {
+                                constexpr auto scales_in_lds = &nf4_gemm_smallm_kernel<DT, MT, D, W, NT, true, SM>;
+                                constexpr auto scales_gathered = &nf4_gemm_smallm_kernel<DT, MT, D, W, NT, false, SM>;
+                                if (vs) hipLaunchKernelGGL(scales_in_lds, grid, block, ls.dyn, st, A);
+                                else hipLaunchKernelGGL(scales_gathered, grid, block, 0, st, A);
+                                rc = hip_rc2(hipGetLastError());
+                            });
                         });
                     });
             });

@@ -6,7 +6,7 @@ namespace nf4gemm {
 
 // One launch of the persistent kernel over `count` weights sharing x (cfg
 // validated per weight and known to run: cfg_runs).  Grid: persist_grid.
-int launch_persist(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
+int NF4_GEMM_FN(launch_persist)(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
                    const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st) {
     StreamArgs S{};
     fill_common(S, count, x, M, K, cfg, workspace);
@@ -30,6 +30,7 @@ int launch_persist(const HostMat* mats, int count, const void* x, int64_t M, int
     }
     S.sg_total = sg;
     S.ncols = strips * 16u;
+    if (count == 1 && mats[0].mode != kScaleRef) fill_mode(S, mats[0]);
     if (cfg_runs(cfg, M, K, mats, count, cus) != NF4DQ_OK) return NF4DQ_ERR_ARG;  // not a plan
     const PersistGrid g = persist_grid(M, K, cfg, sg, cus);
     S.zero_off = g.zero_off;
@@ -40,7 +41,10 @@ int launch_persist(const HostMat* mats, int count, const void* x, int64_t M, int
         pick<4, 8, 16>(cfg.waves, [&](auto W) {
             pick<2, 4>(cfg.depth, [&](auto P) {
                 pick<true, false>(S.ksplit > 1, [&](auto SPLIT) {
-                    launch_lds<&nf4_gemm_persist_kernel<DT, W, P, SPLIT>>(kStreamLdsCap, grid, block, g.dyn, st, S);
+                    pick<NF4_GEMM_MODES>(count > 0 ? mats[0].mode : kScaleRef, [&](auto SM) {
+                        launch_lds<&nf4_gemm_persist_kernel<DT, W, P, SPLIT, SM>>(kStreamLdsCap, grid, block, g.dyn, st,
+                                                                                   S);
+                    });
                 });
             });
         });

@@ -4,7 +4,7 @@
 
 namespace nf4gemm {
 
-int launch_xr(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
+int NF4_GEMM_FN(launch_xr)(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
               const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st) {
     GemmArgs A{};
     fill_common(A, count, x, M, K, cfg, workspace);
@@ -20,7 +20,8 @@ int launch_xr(const HostMat* mats, int count, const void* x, int64_t M, int64_t 
     }
     A.col_groups = strips;
     A.ncols = strips * 16u;
-    A.per_wg = xr_per_wg(M, strips, cfg, cus);
+    if (count > 0) fill_mode(A, mats[0]);
+    A.per_wg = xr_per_wg(M, strips, cfg, cus, count > 0 ? mats[0].mode : kScaleRef);
     const LaunchShape ls = launch_shape(cfg, M, K, mats, count, cus);
     const uint32_t ks = A.ksplit, lds = ls.dyn;
     const dim3 grid(ls.grid), block(ls.block);
@@ -39,13 +40,15 @@ int launch_xr(const HostMat* mats, int count, const void* x, int64_t M, int64_t 
                         pick<4, 2>(cfg.depth, [&](auto D) {
                             pick<4, 8, 0>(gu, [&](auto GU) {
                                 if constexpr (GU == 0 || (W == 8 && KPW == 2 && D == 2)) {
-                                    const uint32_t cap = kLdsPerCu - xr_lds_static(KPW);
-                                    // both templates are instantiated for every GU, as ever
-                                    constexpr auto xrg = &nf4_gemm_xrg_kernel<DT, MT, W, KPW, D, GU>;
-                                    constexpr auto xr = &nf4_gemm_xr_kernel<DT, MT, W, KPW, D, GU>;
-                                    if (GU) launch_lds<xrg>(cap, grid, block, lds, st, A);
-                                    else launch_lds<xr>(cap, grid, block, lds, st, A);
-                                    rc = hip_rc2(hipGetLastError());
+                                    pick<NF4_GEMM_MODES>(count > 0 ? mats[0].mode : kScaleRef, [&](auto SM) {
+                                        const uint32_t cap = kLdsPerCu - xr_lds_static(KPW, SM);
+                                        // both templates are instantiated for every GU, as ever
+                                        constexpr auto xrg = &nf4_gemm_xrg_kernel<DT, MT, W, KPW, D, GU, SM>;
+                                        constexpr auto xr = &nf4_gemm_xr_kernel<DT, MT, W, KPW, D, GU, SM>;
+                                        if (GU) launch_lds<xrg>(cap, grid, block, lds, st, A);
+                                        else launch_lds<xr>(cap, grid, block, lds, st, A);
+                                        rc = hip_rc2(hipGetLastError());
+                                    });
                                 }
                             });
                         });

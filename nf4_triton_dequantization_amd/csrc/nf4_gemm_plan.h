@@ -35,21 +35,35 @@ constexpr size_t kCounterBytes = 64 * 1024;
 constexpr size_t kHeaderBytes = kCounterBytes + 256;
 static_assert(kErrWord * 4u == kCounterBytes, "the error word follows the counters");
 
+// How a 64-block's scale is made (a compile-time mode of the kernel families that have it):
+//  * kScaleRef: the reference repository's, (a1[i] / 127) * a2[row group], statistics
+//    repeating (wrap) -- nf4_gemm_ref and its kin;
+//  * kScaleBnb: bitsandbytes nested, code2[a1[i]] * a2[i >> sh2] + offset (two roundings)
+//    with i = (flat 64-block) >> sh, no wrap -- nf4_gemm_bnb;
+//  * kScaleBnbSingle: bitsandbytes with fp32 statistics, a2[i] -- nf4_gemm_bnb_single.
+constexpr int kScaleRef = 0, kScaleBnb = 1, kScaleBnbSingle = 2;
+
 // One weight of a launch (host view).
 struct HostMat {
     const uint8_t* packed;
     int64_t packed_len;
     const uint8_t* a1;
     int64_t nb;
-    const float* a2;
+    const float* a2;  // kScaleBnbSingle: the fp32 absmax (nb = n2 = its length, a1 unused)
     int64_t n2;
     void* y;
     int64_t N;
+    // bitsandbytes modes (nf4_gemm_bnb*); the reference entries leave the defaults
+    int mode = kScaleRef;
+    const float* code2 = nullptr;   // 256 fp32 (device)
+    const float* offset = nullptr;  // 1 fp32 (device); null = 0
+    int sh = 0, sh2 = 0;            // log2(blocksize / 64), log2(blocksize2)
 };
 
 // No row's absmax bytes or nested scales wrap around inside the row (what the
 // persistent kernel, the GEMV and the vector-scale forms assume).
 inline bool no_wrap_in_row(const HostMat& h, int64_t K) {
+    if (h.mode != kScaleRef) return true;  // a flat stream of statistics: nothing repeats
     const int64_t bpr = K / 64, groups = (bpr + 3) / 4;
     if (bpr == 0) return false;  // K = 0: no row to speak of, and no cfg that needs this runs
     return (h.nb % bpr == 0 || h.nb >= h.N * bpr) && (h.n2 % groups == 0 || h.n2 >= h.N * groups);
@@ -134,24 +148,26 @@ inline uint32_t xs_lds_bytes(int64_t M, int kc, int waves) {
 // Register-resident kernel: grid = ksplit x (strip groups of T strips); T from
 // the CUs the launch can hold at once (one 16-wave workgroup per CU), at most 64
 // (ticket flags) and within LDS.
-inline uint32_t xr_lds_static(int kpw) {  // pair table + q/127 (256-deep chunks), static in the kernel
-    return kpw >= 2 ? 256u * 32u * 8u + 1024u : 64u;
+// (128-deep chunks keep no table in the reference mode; the nested bnb mode's code2 table is
+// static there too)
+constexpr uint32_t xr_lds_static(int kpw, int mode = kScaleRef) {  // pair table + q/127 or code2, static in the kernel
+    return kpw >= 2 ? 256u * 32u * 8u + 1024u : mode == kScaleBnb ? 64u + 1024u : 64u;
 }
 inline uint32_t xr_lds_dynamic(int64_t M, int waves, uint32_t T) {
     const uint32_t mt = M > 16 ? 2u : 1u;
     const uint32_t r = waves == 8 ? 2u : 1u;  // strips per reduction group (kernel's R; depth is even)
     return 2u * r * (uint32_t)waves * mt * 1024u + 64u + 256u + T * mt * 1024u;  // partials, codes, flags, held
 }
-inline uint32_t xr_lds_bytes(int64_t M, int waves, int kpw, uint32_t T) {
-    return xr_lds_static(kpw) + xr_lds_dynamic(M, waves, T);
+inline uint32_t xr_lds_bytes(int64_t M, int waves, int kpw, uint32_t T, int mode = kScaleRef) {
+    return xr_lds_static(kpw, mode) + xr_lds_dynamic(M, waves, T);
 }
 
-inline uint32_t xr_per_wg(int64_t M, int64_t strips, const nf4_gemm_cfg& c, int cus) {
+inline uint32_t xr_per_wg(int64_t M, int64_t strips, const nf4_gemm_cfg& c, int cus, int mode = kScaleRef) {
     const uint32_t wg_per_cu = c.waves == 16 || c.strips >= 2 ? 1u : 2u;  // the pair table leaves room for one
     uint32_t P = (uint32_t)cus * wg_per_cu / (uint32_t)c.ksplit;          // workgroups per K slice
     if (P < 1) P = 1;
     uint32_t T = (uint32_t)((strips + P - 1) / P);
-    while (T > 1 && (T > 64 || xr_lds_bytes(M, c.waves, c.strips, T) > kLdsPerCu)) T = (T + 1) / 2;
+    while (T > 1 && (T > 64 || xr_lds_bytes(M, c.waves, c.strips, T, mode) > kLdsPerCu)) T = (T + 1) / 2;
     return T < 1 ? 1u : T;
 }
 
@@ -201,7 +217,7 @@ inline LaunchShape launch_shape(const nf4_gemm_cfg& c, int64_t M, int64_t K, con
             l.dyn = xs_lds_bytes(M, c.depth, c.waves);
             break;
         case NF4DQ_GEMM_XR: {
-            const uint32_t per_wg = xr_per_wg(M, rows / 16u, c, cus);
+            const uint32_t per_wg = xr_per_wg(M, rows / 16u, c, cus, count > 0 ? mats[0].mode : kScaleRef);
             l.grid = (rows / 16u + per_wg - 1) / per_wg * ks;
             l.dyn = xr_lds_dynamic(M, c.waves, per_wg);
             break;
@@ -326,6 +342,22 @@ inline nf4_gemm_cfg k128_cfg(int64_t M, int64_t N, int64_t K, int waves, int dep
     return c;
 }
 
+// The 128-deep decomposition for a shape no other family takes: what nonpersist_cfg ends
+// with (after its streaming, register-resident and shared-activation choices), and what the
+// bnb plan substitutes for a family without the mode (bnb_choice).
+inline nf4_gemm_cfg k128_tail_cfg(int64_t M, int64_t N, int64_t K) {
+    if (M <= 16) {
+        if (K >= 8192) return k128_cfg(M, N, K, 8, 1, 2, 2);
+        if (N < 4096) return k128_cfg(M, N, K, 4, 2, 4, 1);
+        return k128_cfg(M, N, K, 8, 2, 1, 1);
+    }
+    if (K >= 8192) return k128_cfg(M, N, K, 8, 1, 4, 4);
+    if (N < 4096) return k128_cfg(M, N, K, 4, 2, 4, 1);
+    if (N <= 4096) return k128_cfg(M, N, K, 8, 1, 2, 2);
+    if (N < 8192) return k128_cfg(M, N, K, 4, 1, 4, 2);
+    return k128_cfg(M, N, K, N >= 16384 ? 4 : 8, 1, 1, 4);
+}
+
 // The library's choice when the persistent kernel is not used (or cannot run:
 // absmax wrapping inside a row, held outputs beyond its LDS).
 inline nf4_gemm_cfg nonpersist_cfg(int64_t M, int64_t N, int64_t K) {
@@ -347,9 +379,7 @@ inline nf4_gemm_cfg nonpersist_cfg(int64_t M, int64_t N, int64_t K) {
             while (c.ksplit < K / kSChunkK && !stream_fits(M, K, c)) ++c.ksplit;
             if (valid_gemm_cfg(c, M, N, K)) return c;
         }
-        if (K >= 8192) return k128_cfg(M, N, K, 8, 1, 2, 2);
-        if (N < 4096) return k128_cfg(M, N, K, 4, 2, 4, 1);
-        return k128_cfg(M, N, K, 8, 2, 1, 1);
+        return k128_tail_cfg(M, N, K);
     }
     if (K % kSChunkK == 0 && N >= 1024) {
         // the register-resident kernel with pair-table lookups, 8 waves x 256-deep
@@ -366,7 +396,7 @@ inline nf4_gemm_cfg nonpersist_cfg(int64_t M, int64_t N, int64_t K) {
         const nf4_gemm_cfg c{NF4DQ_GEMM_XR, 8, 2, (int)((K / kChunkK + 15) / 16), 2};
         if (valid_gemm_cfg(c, M, N, K)) return c;
     }
-    if (K >= 8192) return k128_cfg(M, N, K, 8, 1, 4, 4);
+    if (K >= 8192) return k128_tail_cfg(M, N, K);
     if (N >= 6144) {
         // wide launches (gate/up, grouped q/k/v): the shared-activation kernel,
         // 10-13 % faster than the 128-deep one at M = 24 / 32 (profiles/r02/sweep_gemm_xs.jsonl)
@@ -374,10 +404,7 @@ inline nf4_gemm_cfg nonpersist_cfg(int64_t M, int64_t N, int64_t K) {
         const nf4_gemm_cfg c{NF4DQ_GEMM_XS, waves, kc, (int)((K / kChunkK + kc - 1) / kc), 1};
         if (valid_gemm_cfg(c, M, N, K)) return c;
     }
-    if (N < 4096) return k128_cfg(M, N, K, 4, 2, 4, 1);
-    if (N <= 4096) return k128_cfg(M, N, K, 8, 1, 2, 2);
-    if (N < 8192) return k128_cfg(M, N, K, 4, 1, 4, 2);
-    return k128_cfg(M, N, K, N >= 16384 ? 4 : 8, 1, 1, 4);
+    return k128_tail_cfg(M, N, K);
 }
 
 inline nf4_gemm_cfg default_gemm_cfg(int64_t M, int64_t N, int64_t K) {
@@ -465,6 +492,42 @@ inline size_t library_workspace(int64_t M, int64_t N, int64_t K) {
     const size_t a = workspace_need(M, N, K, default_gemm_cfg(M, N, K));
     const size_t b = workspace_need(M, N, K, nonpersist_cfg(M, N, K));
     return a > b ? a : b;
+}
+
+// ---- bitsandbytes semantics (nf4_gemm_bnb / nf4_gemm_bnb_single) ---------------
+// The families that have the bnb scale modes: the ones the library chooses for model
+// shapes (decode GEMV, persistent, register-resident) and the 128-deep kernel, which
+// takes every accepted shape.  The streaming and shared-activation kernels do not.
+inline bool bnb_has_mode(int kernel) {
+    return kernel == NF4DQ_GEMM_K128 || kernel == NF4DQ_GEMM_XR || kernel == NF4DQ_GEMM_PERSIST ||
+           kernel == NF4DQ_GEMM_GEMV;
+}
+// Statistics blocks above 64 (sh > 0) go through the 128-deep kernel alone: the others'
+// statistic loads assume one byte per 64-block.
+inline bool bnb_cfg_ok(const nf4_gemm_cfg& c, const HostMat& h) {
+    return bnb_has_mode(c.kernel) && (h.sh == 0 || c.kernel == NF4DQ_GEMM_K128);
+}
+
+// What a bnb call runs without a cfg: the reference plan's launch for (M, N, K) -- same
+// family, same decomposition -- or the 128-deep substitute where that family lacks the
+// mode or the weight's blocksize.  One weight, one launch.
+inline Choice bnb_choice(int64_t M, int64_t K, const HostMat& h, int cus) {
+    const Choice ref = library_choice(M, K, &h, 1, cus);
+    nf4_gemm_cfg c = launch_cfg(ref, M, K, h);
+    if (!bnb_cfg_ok(c, h) || !valid_gemm_cfg(c, M, h.N, K)) c = k128_tail_cfg(M, h.N, K);
+    return Choice{c, c, false};
+}
+
+// What nf4_gemm_bnb_workspace_bytes answers without a cfg.  The blocksize and the CU count
+// are not known there: the largest need of what bnb_choice can come to.
+inline size_t bnb_library_workspace(int64_t M, int64_t N, int64_t K) {
+    size_t w = workspace_need(M, N, K, k128_tail_cfg(M, N, K));
+    const nf4_gemm_cfg cs[2] = {default_gemm_cfg(M, N, K), nonpersist_cfg(M, N, K)};
+    for (const nf4_gemm_cfg& c : cs) {
+        const size_t wc = bnb_has_mode(c.kernel) ? workspace_need(M, N, K, c) : 0;
+        w = wc > w ? wc : w;
+    }
+    return w;
 }
 
 // Grouped: the cfg's need over the column total; the library's persistent choice may

@@ -24,7 +24,8 @@ no silent fallback: compute always goes through ``libnf4dq.so``.
 Extensions beyond the reference: ``dequantize_nf4_many`` (one
 launch for many weights), ``dequantize_nf4_bnb`` (bitsandbytes semantics,
 parity unpinned), ``dequantize_nf4_into`` (caller-provided output) and the
-consumer ``x @ W.t()`` fused: ``nf4_linear`` / ``nf4_linear_grouped``.
+consumer ``x @ W.t()`` fused: ``nf4_linear`` / ``nf4_linear_grouped`` (reference
+semantics) and ``nf4_linear_bnb`` (bitsandbytes semantics, what ``Linear4bit.forward`` runs).
 """
 from __future__ import annotations
 
@@ -514,6 +515,109 @@ def nf4_linear(x: torch.Tensor, module, bias: Optional[torch.Tensor] = None) -> 
     if bias is not None:
         y = y + bias.to(y.dtype)
     return y.reshape(*lead, N)
+
+
+def _offset_ptr(off, device):
+    """``quant_state.offset`` as (tensor kept alive, device pointer): never a host read.
+    A device tensor passes as it is (the kernel reads its one float when it runs), a Python
+    number becomes a device scalar, None a null pointer (= 0)."""
+    if off is None:
+        return None, None
+    if not torch.is_tensor(off):
+        off = torch.tensor(float(off), dtype=torch.float32, device=device)
+    if off.device != device or off.dtype != torch.float32:
+        off = off.to(device=device, dtype=torch.float32)  # stream-ordered copy, no synchronisation
+    if off.numel() != 1:
+        raise RuntimeError(f"nf4_linear_bnb: quant_state.offset has {off.numel()} elements, expected 1")
+    return off, off.data_ptr()
+
+
+def _bnb_gemm_blocksizes(qs) -> bool:
+    """The statistics block sizes the fused bnb GEMM takes: blocksize a power of two in
+    64..4096 and, when nested, blocksize2 a power of two >= 4 (others dequantize + matmul)."""
+    bs = int(qs.blocksize)
+    if bs < 64 or bs > 4096 or bs & (bs - 1):
+        return False
+    if getattr(qs, "state2", None) is not None and qs.absmax.dtype == torch.uint8:
+        bs2 = int(qs.state2.blocksize)
+        return bs2 >= 4 and not bs2 & (bs2 - 1)
+    return True
+
+
+def nf4_linear_bnb(x: torch.Tensor, module, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``x @ W.t() (+ bias)`` for a ``Linear4bit`` weight W in bitsandbytes semantics.
+
+    W is what ``dequantize_nf4_bnb(module)`` returns, bit for bit: nested statistics
+    (``code2[absmax] * absmax2 + offset``) or plain fp32 ``absmax``
+    (``compress_statistics=False``), chosen as ``dequantize_nf4_bnb`` chooses.  Decode-shaped
+    inputs run ONE fused launch (``nf4_gemm_bnb`` / ``nf4_gemm_bnb_single``): the 4-bit
+    weight is read once, dequantized in registers and multiplied with fp32 accumulation;
+    ``offset`` is read on the device, so the call never synchronises with the host.  The
+    fused path is taken when the weight is on a GPU, ``quant_state.dtype`` is fp16 or bf16,
+    0 < M <= ``GEMM_MAX_M`` rows, N % 64 == 0, K % 128 == 0, the packed weight is uint8 of
+    N * K / 2 bytes, ``quant_type`` is nf4 and no gradient is being recorded for ``x`` (the
+    fused call is not differentiable).  Everything else dequantizes with the HIP kernel and
+    multiplies with torch, which autograd follows.  Both paths use the same weights and fp32
+    accumulation; the summation order differs, so the last bit of ``y`` may.
+    """
+    weight = module.weight
+    qs = weight.quant_state
+    qweight = weight.data
+    dtype = qs.dtype
+    N, K = int(module.out_features), int(module.in_features)
+    if qweight.device.type == "cuda":
+        _same_device(x, qweight)
+    if x.shape[-1] != K:
+        raise RuntimeError(f"nf4_linear_bnb: x has {x.shape[-1]} features, weight expects {K}")
+    lead = x.shape[:-1]
+    M = x.numel() // K if K else 0
+    fused = (qweight.device.type == "cuda" and dtype in (torch.float16, torch.bfloat16)
+             and 0 < M <= _lib.GEMM_MAX_M and N % 64 == 0 and K % 128 == 0
+             and qweight.dtype == torch.uint8 and qweight.numel() == N * K // 2
+             and getattr(qs, "quant_type", None) == "nf4" and _bnb_gemm_blocksizes(qs)
+             and not (torch.is_grad_enabled() and x.requires_grad))
+    if not fused:
+        w = dequantize_nf4_bnb(module)
+        y = x.to(w.dtype) @ w.t()
+    else:
+        dev = qweight.device
+        xc = x.reshape(M, K)
+        if xc.dtype != dtype:
+            xc = xc.to(dtype)
+        xc = xc.contiguous()
+        y = torch.empty((M, N), dtype=dtype, device=dev)
+        L = _lib.lib()
+        bs = int(qs.blocksize)
+        nested = getattr(qs, "state2", None) is not None and qs.absmax.dtype == torch.uint8  # as _launch_bnb
+        with torch.cuda.device(dev):
+            ws_bytes = L.nf4_gemm_bnb_workspace_bytes(M, N, K, None)
+            ws = _gemm_workspace(dev, ws_bytes) if ws_bytes else None
+            wp = ws.data_ptr() if ws is not None else None
+            q, qp, qn = _flat_ptr(qweight)
+            stream = torch.cuda.current_stream().cuda_stream
+            if nested:
+                _on_device(dev, qs.absmax, qs.state2.code, qs.state2.absmax)
+                a1, ap, an = _flat_ptr(qs.absmax)
+                c2 = qs.state2.code
+                c2, cp, cn = _flat_ptr(c2 if c2.dtype == torch.float32 else c2.to(torch.float32))
+                a2 = qs.state2.absmax
+                a2, bp, bn = _flat_ptr(a2 if a2.dtype == torch.float32 else a2.to(torch.float32))
+                if cn != 256:
+                    raise RuntimeError(f"nf4_linear_bnb: state2.code has {cn} entries, expected 256")
+                off, op = _offset_ptr(qs.offset, dev)
+                rc = L.nf4_gemm_bnb(xc.data_ptr(), M, qp, qn, ap, an, cp, bp, bn, op, bs, int(qs.state2.blocksize),
+                                    y.data_ptr(), _dtype_code(dtype), N, K, wp, ws_bytes, None, stream)
+            else:
+                _on_device(dev, qs.absmax)
+                am = qs.absmax
+                am, ap, an = _flat_ptr(am if am.dtype == torch.float32 else am.to(torch.float32))
+                rc = L.nf4_gemm_bnb_single(xc.data_ptr(), M, qp, qn, ap, an, bs, y.data_ptr(), _dtype_code(dtype),
+                                           N, K, wp, ws_bytes, None, stream)
+        _lib.check(rc, "nf4 fused bnb gemm")
+        y = y.reshape(*lead, N)
+    if bias is not None:
+        y = y + bias.to(y.dtype)
+    return y
 
 
 def nf4_linear_grouped(x: torch.Tensor, modules: Sequence, biases: Optional[Sequence] = None) -> List[torch.Tensor]:

@@ -14,6 +14,19 @@ each pass streams them from HBM.  Per M, hipGraph replay of one full pass:
 
 Roofline of the fused kernel: HBM bytes = N*K/2 packed + N*K/64 absmax + nested
 absmax + x + y per weight, vs 8 TB/s.
+
+``--semantics bnb``: the bitsandbytes-semantics path.  The weights come from
+``nf4_quantize`` (nested statistics, blocksize 64).  Per shape of ``--shapes`` and per M, a
+rotation of distinct weights larger than the Infinity Cache, and then the whole pass:
+
+  bnb        nf4_gemm_bnb per weight, hipGraph replay
+  ref        nf4_gemm_ref on the same packed bytes and statistics arrays (same traffic,
+             the reference scale), replayed in turn with bnb: ``rounds`` interleaved pairs
+  forward    Linear4bit.forward (nf4_linear_bnb: one fused launch), eager, wall clock
+  unfused    what forward did before: dequantize_nf4_bnb (host read of the offset) + matmul,
+             eager, wall clock
+
+One JSON line per (shape, M) with medians, min - max of the rounds and the ratios.
 """
 from __future__ import annotations
 
@@ -53,8 +66,136 @@ def graph_ms(fn, reps=5):
     return ts[len(ts) // 2]
 
 
+def _wall_us(fn, n, reps=3):
+    """Median wall-clock microseconds per call of fn(i), i < n, host work and waits included."""
+    import time
+
+    ts = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(n):
+            fn(i)
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e6 / n)
+    ts.sort()
+    return ts[len(ts) // 2]
+
+
+def _interleaved_us(fa, fb, n, rounds=5):
+    """fa and fb (n launches each) captured once, replayed in turn; per-launch microseconds
+    of every round."""
+    graphs = []
+    for fn in (fa, fb):
+        fn()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            fn()
+        g.replay()
+        graphs.append(g)
+    torch.cuda.synchronize()
+    st = torch.cuda.current_stream()
+    out = ([], [])
+    for _ in range(rounds):
+        for g, ts in zip(graphs, out):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            g.replay()
+            e1.record(st)
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e3 / n)
+    return [sorted(t) for t in out]
+
+
+def _stats(ts):
+    return {"med": round(ts[len(ts) // 2], 3), "min": round(ts[0], 3), "max": round(ts[-1], 3)}
+
+
+def main_bnb(args):
+    from nf4_triton_dequantization_amd import Linear4bit, dequantize_nf4_bnb
+
+    dev = torch.device("cuda", 0)
+    L = _lib.lib()
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(0)
+
+    def quantized(n, k):
+        w = torch.randn((n, k), device=dev, generator=gen, dtype=torch.bfloat16) * 0.02
+        return Linear4bit.from_float(w, compute_dtype=torch.bfloat16)
+
+    def measure(label, mods, M):
+        """mods: the weights one pass goes through, in order."""
+        ks = {m.in_features for m in mods}
+        xs = {k: torch.randn((M, k), device=dev, generator=gen).to(torch.bfloat16) for k in ks}
+        ys = [torch.empty((M, m.out_features), dtype=torch.bfloat16, device=dev) for m in mods]
+        wsz = max(max(L.nf4_gemm_bnb_workspace_bytes(M, m.out_features, m.in_features, None),
+                      L.nf4_gemm_workspace_bytes(M, m.out_features, m.in_features)) for m in mods)
+        work = torch.zeros(max(wsz, 1 << 16), dtype=torch.uint8, device=dev)
+        t = []
+        for m in mods:
+            qs = m.weight.quant_state
+            t.append((m.weight.data, qs.absmax, qs.state2.code, qs.state2.absmax, qs.offset))
+
+        def bnb():
+            sp = torch.cuda.current_stream().cuda_stream
+            for m, y, (q, a1, c2, a2, off) in zip(mods, ys, t):
+                rc = L.nf4_gemm_bnb(xs[m.in_features].data_ptr(), M, q.data_ptr(), q.numel(), a1.data_ptr(), a1.numel(),
+                                    c2.data_ptr(), a2.data_ptr(), a2.numel(), off.data_ptr(), 64, 256, y.data_ptr(),
+                                    _lib.BF16, m.out_features, m.in_features, work.data_ptr(), wsz, None, sp)
+                assert rc == 0, rc
+
+        def ref():
+            sp = torch.cuda.current_stream().cuda_stream
+            for m, y, (q, a1, _c2, a2, _off) in zip(mods, ys, t):
+                rc = L.nf4_gemm_ref(xs[m.in_features].data_ptr(), M, q.data_ptr(), q.numel(), a1.data_ptr(), a1.numel(),
+                                    a2.data_ptr(), a2.numel(), y.data_ptr(), _lib.BF16, m.out_features, m.in_features,
+                                    work.data_ptr(), wsz, sp)
+                assert rc == 0, rc
+
+        tb, tr = _interleaved_us(bnb, ref, len(mods), args.rounds)
+        if wsz:
+            assert L.nf4_gemm_check_workspace(work.data_ptr(), wsz, torch.cuda.current_stream().cuda_stream) == 0
+
+        def forward(i):
+            mods[i](xs[mods[i].in_features])
+
+        def unfused(i):  # Linear4bit.forward before the fused path
+            w = dequantize_nf4_bnb(mods[i])
+            xs[mods[i].in_features].to(w.dtype) @ w.t()
+
+        with torch.no_grad():
+            forward(0), unfused(0)
+            fw, un = _wall_us(forward, len(mods)), _wall_us(unfused, len(mods))
+        res = {"semantics": "bnb", "what": label, "M": M, "launches": len(mods), "bnb_us": _stats(tb),
+               "ref_us": _stats(tr), "bnb_over_ref": round(tb[len(tb) // 2] / tr[len(tr) // 2], 4),
+               "forward_eager_us": round(fw, 3), "unfused_eager_us": round(un, 3),
+               "unfused_over_forward": round(un / fw, 3), "unfused_over_bnb_graph": round(un / tb[len(tb) // 2], 3)}
+        if label == "pass":
+            res["bnb_pass_ms"] = round(tb[len(tb) // 2] * len(mods) / 1e3, 4)
+            res["ref_pass_ms"] = round(tr[len(tr) // 2] * len(mods) / 1e3, 4)
+        print(json.dumps(res), flush=True)
+
+    ms = [int(v) for v in args.ms.split(",")]
+    for sh in [s for s in args.shapes.split(";") if s]:
+        n, k = (int(v) for v in sh.split(","))
+        copies = max(8, args.budget_mb * (1 << 20) // (n * k // 2))
+        mods = [quantized(n, k) for _ in range(copies)]
+        for M in ms:
+            measure(f"{n}x{k}", mods, M)
+        del mods
+    if args.layers > 0:
+        mods = [quantized(n, k) for _ in range(args.layers) for (n, k) in SHAPES]
+        for M in ms:
+            measure("pass", mods, M)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--semantics", choices=["ref", "bnb"], default="ref")
+    ap.add_argument("--shapes", default="4096,4096;14336,4096;4096,14336", help="--semantics bnb: N,K;N,K;...")
+    ap.add_argument("--budget-mb", type=int, default=768, help="--semantics bnb: packed bytes of a shape's rotation")
+    ap.add_argument("--rounds", type=int, default=5, help="--semantics bnb: interleaved replay pairs")
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--ms", default="1,4,8,16,32")
     ap.add_argument("--no-bf16", action="store_true")
@@ -63,6 +204,8 @@ def main():
     args = ap.parse_args()
     if args.lib != "prod":
         _lib.LIB_PATH = os.path.join(REPO, "tools", "_build", f"libnf4dq_{args.lib}.so")
+    if args.semantics == "bnb":
+        return main_bnb(args)
     dev = torch.device("cuda", 0)
     L = _lib.lib()
     gen = torch.Generator(device=dev)

@@ -15,6 +15,13 @@ grouped M = 1 launches (2-4 weights in multiples of 64 columns sharing x, some w
 wrapping at row boundaries): up to 4096 columns in all through the library's choice, or up
 to 8192 with a drawn GEMV configuration; each output against its own oracle. One progress
 line per 100 cases, then a summary.
+
+``--semantics bnb``: the bitsandbytes-semantics entries instead. Each case quantizes a drawn
+float weight with ``nf4_quantize`` (nested or plain fp32 statistics, blocksize 64 / 128 / 512
+/ 4096), runs ``Linear4bit.forward`` (``nf4_linear_bnb``, the library's choice) and, for
+``--cfg-rate`` of the cases, a drawn configuration through ``nf4_gemm_bnb`` /
+``nf4_gemm_bnb_single`` (a family without the mode is rejected and skipped); the oracle is
+the C oracle's ``dequant_bnb`` / ``dequant_bnb_single``, same tolerance.
 """
 from __future__ import annotations
 
@@ -128,8 +135,75 @@ def grouped_gemv_case(rng, L, orc, dev):
     return out, label
 
 
+def bnb_case(rng, L, orc, dev, cfg_rate):
+    """One bitsandbytes-semantics case; returns (mismatch records, explicit cfg runs)."""
+    from nf4_triton_dequantization_amd import Linear4bit
+
+    M = int(rng.integers(1, 33))
+    N = 64 * int(rng.integers(1, 49))
+    K = 128 * int(rng.integers(1, 49))
+    if rng.random() < 0.15:  # the decode GEMV's domain
+        M, N, K = 1, 64 * int(rng.integers(1, 65)), 2048 * int(rng.integers(1, 4))
+    dt = "bf16" if rng.random() < 0.6 else "f16"
+    tdt = torch.bfloat16 if dt == "bf16" else torch.float16
+    nested = bool(rng.random() < 0.7)
+    bs = int(rng.choice([64, 64, 64, 128, 512, 4096]))
+    seed = int(rng.integers(1, 1 << 30))
+    wf = torch.from_numpy(O.normal_f32(seed, N * K, stream=8).reshape(N, K)).to(dev) * float(rng.choice([0.02, 1.0]))
+    mod = Linear4bit.from_float(wf, compute_dtype=tdt, compress_statistics=nested, blocksize=bs)
+    qs = mod.weight.quant_state
+    packed = mod.weight.data.view(-1).cpu().numpy()
+    code = O.BF16 if dt == "bf16" else O.F16
+    if nested:
+        w = orc.dequant_bnb(packed, qs.absmax.cpu().numpy(), qs.state2.code.cpu().numpy(),
+                            qs.state2.absmax.cpu().numpy(), float(qs.offset), N * K, code, bs, int(qs.state2.blocksize))
+    else:
+        w = orc.dequant_bnb_single(packed, qs.absmax.cpu().numpy(), N * K, code, bs)
+    x = O.normal_f32(seed + 1, M * K, stream=9).reshape(M, K)
+    xt = torch.from_numpy(x).to(tdt)
+    xb = xt.view(torch.int16).numpy().view(np.uint16)
+    xf, wf64 = bits_to_f64(xb, dt), bits_to_f64(w.reshape(N, K), dt)
+    ref = xf @ wf64.T
+    bound = tol(ref, np.abs(xf) @ np.abs(wf64).T, dt)
+    xd = xt.to(dev)
+    with torch.no_grad():
+        outs = [("default", mod(xd))]
+    info = {"semantics": "bnb", "M": M, "N": N, "K": K, "dtype": dt, "seed": seed, "nested": nested, "blocksize": bs}
+    records, ran = [], 0
+    if rng.random() < cfg_rate:
+        cfg = random_cfg(rng, M, N, K)
+        wsz = L.nf4_gemm_bnb_workspace_bytes(M, N, K, ctypes.byref(cfg))
+        ws = torch.zeros(max(wsz, 16), dtype=torch.uint8, device=dev)
+        y = torch.empty((M, N), dtype=tdt, device=dev)
+        q = mod.weight.data
+        sp = torch.cuda.current_stream().cuda_stream
+        tail = (y.data_ptr(), _lib.BF16 if dt == "bf16" else _lib.F16, N, K, ws.data_ptr() if wsz else None, wsz,
+                ctypes.byref(cfg), sp)
+        if nested:
+            rc = L.nf4_gemm_bnb(xd.data_ptr(), M, q.data_ptr(), q.numel(), qs.absmax.data_ptr(), qs.absmax.numel(),
+                                qs.state2.code.data_ptr(), qs.state2.absmax.data_ptr(), qs.state2.absmax.numel(),
+                                qs.offset.data_ptr(), bs, int(qs.state2.blocksize), *tail)
+        else:
+            rc = L.nf4_gemm_bnb_single(xd.data_ptr(), M, q.data_ptr(), q.numel(), qs.absmax.data_ptr(),
+                                       qs.absmax.numel(), bs, *tail)
+        if rc == 0:
+            ran = 1
+            label = [cfg.kernel, cfg.waves, cfg.depth, cfg.ksplit, cfg.strips]
+            if wsz and L.nf4_gemm_check_workspace(ws.data_ptr(), wsz, sp):
+                records.append(dict(info, timeout=True, path=label))
+            outs.append((label, y))
+    for label, y in outs:
+        got = bits_to_f64(y.contiguous().view(torch.int16).cpu().numpy().view(np.uint16), dt).reshape(M, N)
+        if not (np.abs(got - ref) <= bound).all():
+            records.append(dict(info, path=label, worst=float(np.nanmax(np.abs(got - ref))),
+                                nan=int(np.isnan(got).sum())))
+    return records, ran
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--semantics", choices=["ref", "bnb"], default="ref",
+                    help="ref: nf4_gemm_ref and its kin; bnb: nf4_gemm_bnb / nf4_gemm_bnb_single on nf4_quantize's weights")
     ap.add_argument("--cases", type=int, default=1500)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--seconds", type=float, default=500.0)
@@ -155,6 +229,15 @@ def main():
     for i in range(args.cases):
         if time.time() - t0 > args.seconds:
             break
+        if args.semantics == "bnb":
+            records, ran = bnb_case(rng, L, orc, dev, args.cfg_rate)
+            for r in records:
+                bad += 1
+                print(json.dumps({"mismatch": r}), flush=True)
+            cfg_runs += ran
+            done += 1
+            progress()
+            continue
         M = int(rng.integers(1, 33))
         N = 64 * int(rng.integers(1, 49))
         K = 128 * int(rng.integers(1, 49))
@@ -220,7 +303,7 @@ def main():
                                                "worst": float(np.abs(got - ref).max())}}), flush=True)
         done += 1
         progress()
-    print(json.dumps({"summary": {"cases": done, "explicit_cfg_runs": cfg_runs, "grouped_runs": grouped_runs,
+    print(json.dumps({"summary": {"semantics": args.semantics, "cases": done, "explicit_cfg_runs": cfg_runs, "grouped_runs": grouped_runs,
                                   "mismatches": bad,
                                   "seed": args.seed, "seconds": round(time.time() - t0, 1)}}), flush=True)
 
