@@ -42,54 +42,26 @@
 //    kernel could not store whole (n % 8 != 0, a misaligned output or packed
 //    weight, fp32 output), in OUTPUT order: 16-byte output pieces stored straight
 //    from registers, the irregularity moved to the packed loads.
+// This file: the kernels, then a thin host side.  What a call launches -- validation, kernel
+// family and form, grid, argument image -- is decided in nf4_dequant_plan.h (plain C++, pinned
+// without a GPU by tests/test_dequant_plan_cpu.py); run() at the end turns each launch of a
+// plan into the kernel launch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/nf4_dequant.h"
 #include "nf4_common.h"
+#include "nf4_dequant_plan.h"
 
 namespace {
 
 using namespace nf4dq;
 
-enum Mode : int { kRef = 0, kSingle = 1, kBnb = 2, kBnbSingle = 3 };
-
-// Kernel-argument image of one matrix on the flat path.
-struct Desc {
-    const uint32_t* packed;  // dense packed stream (4-byte aligned)
-    const uint8_t* a1;       // uint8 absmax (ref, bnb)
-    const float* a2;         // nested absmax (ref, bnb) or fp32 absmax (single modes)
-    const float* code2;      // bnb nested code book (256 fp32)
-    u32x4* out;              // 16-byte aligned output
-    float offset;            // bnb offset
-    uint32_t nbytes;         // packed bytes (multiple of 4)
-    uint32_t tile_begin;     // first tile of this matrix within the launch
-    uint32_t groups;         // ceil(bpr/4) (ref)
-    FastDiv nb;              // ref: modulus of A1 index
-    FastDiv n2;              // ref: modulus of A2 index; single: .d = row stride
-    FastDiv bpr;             // blocks per row
-    uint32_t blk_shift;      // log2(bytes per scale block)
-    uint32_t blk2_shift;     // bnb: log2(blocksize2)
-    uint32_t blk_base;       // scale blocks before this piece (a matrix above kPieceBytes is several pieces)
-};
-
 // Diagnostic build only (tools/Makefile `stamps`): per-wave s_memrealtime stamps of
 // the flat kernel -- entry, first tile decoded and stored (its loads arrived), exit
 // after its stores completed, tiles walked -- into a buffer set by nf4_dbg_set_stamps.
-#ifndef NF4_FLAT_STAMPS
-#define NF4_FLAT_STAMPS 0
-#endif
-
-template <int MAXB>
-struct Batch {
-    Desc d[MAXB];
-    uint32_t count;
-    uint32_t total_tiles;
-#if NF4_FLAT_STAMPS
-    unsigned long long* stamps;
-#endif
-};
-
 #if NF4_FLAT_STAMPS
 #define NF4_FSTAMP(slot_, val_)                                                                      \
     do {                                                                                             \
@@ -140,15 +112,7 @@ __device__ __forceinline__ void store1(void* out, int64_t i, float x) {
 //   NF4_DQ_FLAT1        1 (product): one matrix under an uncapped grid goes to nf4_flat1_kernel
 //                       (scalar arguments, kernarg preload); 0 = nf4_flat_kernel<.., 1> as before
 //                       (profiles/flat1/)
-#ifndef NF4_DQ_FLAT1
-#define NF4_DQ_FLAT1 1
-#endif
-#ifndef NF4_DQ_FLAT_WAVES
-#define NF4_DQ_FLAT_WAVES 4
-#endif
-#ifndef NF4_DQ_U
-#define NF4_DQ_U 4
-#endif
+// (the defaults of FLAT_WAVES, U and FLAT1, which the host side sees too: nf4_dequant_plan.h)
 #ifndef NF4_DQ_AUX_STORE
 #define NF4_DQ_AUX_STORE 18
 #endif
@@ -171,13 +135,6 @@ __device__ __forceinline__ void store1(void* out, int64_t i, float x) {
 #define NF4_DQ_ABL_NOSCALE 0
 #endif
 
-
-
-constexpr int kWg = 256;   // rows / bitsandbytes-bytes kernels: 4 waves per workgroup
-constexpr int kFlatWaves = NF4_DQ_FLAT_WAVES;  // the flat kernel's workgroup
-constexpr int kFlatWg = 64 * kFlatWaves;
-constexpr int kU = NF4_DQ_U;  // packed dwords (fp32 output: words) per lane per tile
-
 // Cache-policy bits of the buffer instructions (aux operand, gfx950 CPol):
 // 2 = nt (streaming), 16 = sc1.  Output stores are sc1+nt: a write-once stream,
 // not kept in the XCD L2 (+25-30 % over default-policy stores, profiles/r01/tune_sweep.log).
@@ -192,16 +149,6 @@ constexpr int kAuxStore = NF4_DQ_AUX_STORE;
 // cache-warm figure becomes 7.45 instead of 6.86 us).  Sc0 / sc1 bits beside nt
 // change nothing (profiles/r04/cache/dequant_variants_4096.jsonl).
 constexpr int kAuxLoad = NF4_DQ_AUX_LOAD;
-
-template <int DT>
-constexpr uint32_t out_bytes_per_packed_byte() { return DT == NF4DQ_F32 ? 8u : 4u; }
-// Packed bytes a lane loads per step j: 4 (-> 8 outputs = 16 B of fp16/bf16) or,
-// for fp32 output, 2 (-> 4 outputs = 16 B).  Either way every lane stores 16 B
-// per step and a wave store instruction covers 1 KiB contiguous.
-template <int DT>
-constexpr uint32_t lane_bytes() { return DT == NF4DQ_F32 ? 2u : 4u; }
-template <int DT>
-constexpr uint32_t tile_bytes() { return 64u * lane_bytes<DT>() * kU; }
 
 // Raw inputs of one wave-tile, loaded ahead of use (software pipeline stage 1).
 struct TileIn {
@@ -422,7 +369,7 @@ __device__ __forceinline__ void make_rsrcs(const Batch<MAXB>& bt, uint32_t k, __
 template <int DT, int MODE, int MAXB>
 __global__ __launch_bounds__(kFlatWg) void nf4_flat_kernel(const Batch<MAXB> bt) {
     __shared__ __attribute__((aligned(16))) float lut[16];
-    __shared__ __attribute__((aligned(16))) float code2s[MODE == kBnb ? 256 : 1];  // bitsandbytes code (every piece's)
+    __shared__ __attribute__((aligned(16))) float code2s[MODE == kBnb ? 256 : 1];  // bitsandbytes code (every segment's)
     constexpr bool kTbl = NF4_DQ_DECODE == 1 && DT != NF4DQ_F32;
     __shared__ __attribute__((aligned(256))) char tbl[kTbl ? kFlatWaves * 2048 : 4];  // 8 block tables per wave
     const uint32_t lane = threadIdx.x & 63u;
@@ -463,7 +410,7 @@ __global__ __launch_bounds__(kFlatWg) void nf4_flat_kernel(const Batch<MAXB> bt)
     // (the table decode could take its two codes from immediates and skip this table and
     // the barrier: measured 8 % slower, profiles/r05/nolut_scalefirst_variants.jsonl)
     write_lut(lut);
-    if constexpr (MODE == kBnb) {  // every piece of a bitsandbytes stream carries the same code
+    if constexpr (MODE == kBnb) {  // every segment of a bitsandbytes stream carries the same code
         // (one 16-B load per lane of wave 0 ahead of everything measured slower, and no
         // table at all only 0.6 % faster: profiles/r05/bnb_mode_code_table.jsonl)
         if constexpr (kFlatWg >= 256) {
@@ -615,15 +562,6 @@ __global__ __launch_bounds__(kFlatWg) void nf4_flat1_kernel(
 // Any shape, reference / single-quant semantics: one thread per packed byte.  Only for
 // matrices past the chunk kernel's 32-bit index limits (below) or when a tuning call
 // asks for it (NF4DQ_CFG_ROWS).
-struct RowsArgs {
-    const uint8_t* packed;
-    const uint8_t* a1;
-    const float* a2;
-    void* out;
-    int64_t m, n, stride, cols_b;  // cols_b = ceil(n/2) packed bytes used per row
-    int64_t nb, n2, bpr, groups, rs;
-};
-
 template <int DT, int MODE>
 __global__ __launch_bounds__(kWg) void nf4_rows_kernel(const RowsArgs A) {
     __shared__ __attribute__((aligned(16))) float lut[16];
@@ -670,22 +608,6 @@ __global__ __launch_bounds__(kWg) void nf4_rows_kernel(const RowsArgs A) {
 //    take one 16-byte store per chunk (n % 8 != 0, or the output off 16-byte alignment)
 //    are staged through LDS and written as aligned 16-byte pieces (store16 / flush16):
 //    17.9 / 15.3 us at 4096 x 4090 / 4095 (28.6 us at 4095 storing from the lanes).
-struct ChunkArgs {
-    const uint8_t* packed;
-    const uint8_t* a1;
-    const float* a2;
-    void* out;
-    uint64_t packed_len;  // bytes (the load range)
-    uint64_t out_elems;   // m * n
-    uint32_t stride;      // packed bytes per row
-    uint32_t n;           // columns
-    uint32_t chunks;      // m * L
-    FastDiv L;            // chunks per row
-    FastDiv bpr;          // 64-column blocks per row
-    uint32_t groups;      // ceil(bpr / 4)
-    FastDiv nb, n2;       // ref: moduli of the absmax / nested-absmax indices
-    uint32_t rs;          // single: absmax per row
-};
 
 constexpr uint32_t kDrop = 0xFFFFFFF0u;  // an offset past every range: load 0 / store dropped
 // Stores narrower than 16 bytes (fp32 elements of odd widths, the end pieces of a staged
@@ -1134,23 +1056,6 @@ __global__ __launch_bounds__(kWg) void nf4_chunk_kernel(const ChunkArgs A) {
 // form) sit in 16 OVERLAPPING groups of 8 blocks -- group q holds blocks 4q .. 4q + 7 -- so
 // the blocks of a piece lie in group tA / 4 and one v_perm per element still forms its
 // table address.
-struct PieceArgs {
-    const uint8_t* packed;  // the packed weight aligned down to 4 bytes
-    const uint8_t* a1;
-    const float* a2;
-    void* line;             // the output's first 128-byte line
-    void* out;
-    uint32_t prange;        // load range from `packed` (bytes)
-    uint32_t kb;            // the weight's first byte, from `packed` (0..3)
-    uint32_t sa;            // the output's first element, from `line` (0..63)
-    uint32_t elems;         // m * n
-    uint32_t n, half;       // columns; ceil(n / 2)
-    uint32_t stride;        // packed bytes per row (>= half; > half: padded rows)
-    FastDiv nf, bpr;        // n; 64-column blocks per row
-    uint32_t groups;        // ceil(bpr / 4)
-    FastDiv nb, n2;         // ref: moduli of the absmax / nested-absmax indices
-    uint32_t rs;            // single: absmax per row
-};
 
 constexpr uint32_t kPieceTbl = 4096;  // a wave's tables: 16 groups x 8 blocks x 16 entries x 2 B
 
@@ -1461,18 +1366,6 @@ __global__ __launch_bounds__(kWg) void nf4_piece32_kernel(const PieceArgs A) {
 }
 
 // Any length, bitsandbytes semantics: one thread per packed byte.
-struct BnbBytesArgs {
-    const uint8_t* packed;
-    const uint8_t* a1;
-    const float* code2;
-    const float* a2;
-    void* out;
-    float offset;
-    int64_t numel;
-    int32_t blk_shift_elems, blk2_shift;
-    int32_t single;
-};
-
 template <int DT>
 __global__ __launch_bounds__(kWg) void nf4_bnb_bytes_kernel(const BnbBytesArgs A) {
     __shared__ __attribute__((aligned(16))) float lut[16];
@@ -1490,21 +1383,10 @@ __global__ __launch_bounds__(kWg) void nf4_bnb_bytes_kernel(const BnbBytesArgs A
 }
 
 // ---------------------------------------------------------------------------
-// host side
+// host side: the entry points ask the plan (nf4_dequant_plan.h) what to launch; run()
+// turns each launch of the plan into the kernel launch
 // ---------------------------------------------------------------------------
 inline int hip_rc(hipError_t e) { return e == hipSuccess ? NF4DQ_OK : NF4DQ_ERR_HIP_BASE + (int)e; }
-
-inline bool valid_dtype(int32_t d) { return d == NF4DQ_F16 || d == NF4DQ_BF16 || d == NF4DQ_F32; }
-
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-inline int ilog2(uint64_t v) {
-    int s = 0;
-    while ((uint64_t(1) << s) < v) ++s;
-    return s;
-}
-
-constexpr nf4_launch_cfg kDefaultCfg = {4, 0, 1, 0};  // measured best at 4096^2 (tools/tune.py)
 
 #if NF4_FLAT_STAMPS
 unsigned long long* g_stamps = nullptr;  // diagnostic build: [wave][4] u64
@@ -1517,16 +1399,29 @@ int cu_count() {
     return cus;
 }
 
-// one_tile: the default grid, every wave owns at most one tile.
+// f(std::integral_constant<int, V>) for the V of the list that equals v (the last one when none does)
+template <int V0, int... Vs, class F>
+void with_const(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V0>{});
+    else if (v == V0) f(std::integral_constant<int, V0>{});
+    else with_const<Vs...>(v, f);
+}
+
 template <int DT, int MODE, int MAXB>
-void launch_one(const Batch<MAXB>& b, uint64_t blocks, bool one_tile, hipStream_t st) {
+void run_flat(const Launch& L, hipStream_t st) {
+#if NF4_FLAT_STAMPS
+    Batch<MAXB> b = L.as<Batch<MAXB>>();
+    b.stamps = g_stamps;
+#else
+    const Batch<MAXB>& b = L.as<Batch<MAXB>>();
+#endif
     if constexpr (MAXB == 1 && NF4_DQ_FLAT1) {
-        if (one_tile) {
+        if (L.family == kFlat1) {
             const Desc& d = b.d[0];
-            nf4_flat1_kernel<DT, MODE><<<dim3((unsigned)blocks), dim3(kFlatWg), 0, st>>>(
-                d.packed, d.nbytes, b.total_tiles, d.out, d.a1, d.a2, d.blk_shift, d.blk_base, d.groups, d.bpr.d,
-                d.bpr.mul, d.bpr.shift, d.nb.d, d.nb.mul, d.nb.shift, d.n2.d, d.n2.mul, d.n2.shift, d.code2, d.offset,
-                d.blk2_shift
+            nf4_flat1_kernel<DT, MODE><<<dim3(L.grid), dim3(L.block), 0, st>>>(
+                d.packed, d.nbytes, b.total_tiles, reinterpret_cast<u32x4*>(d.out), d.a1, d.a2, d.blk_shift,
+                d.blk_base, d.groups, d.bpr.d, d.bpr.mul, d.bpr.shift, d.nb.d, d.nb.mul, d.nb.shift, d.n2.d, d.n2.mul,
+                d.n2.shift, d.code2, d.offset, d.blk2_shift
 #if NF4_FLAT_STAMPS
                 , b.stamps
 #endif
@@ -1534,321 +1429,60 @@ void launch_one(const Batch<MAXB>& b, uint64_t blocks, bool one_tile, hipStream_
             return;
         }
     }
-    hipLaunchKernelGGL((nf4_flat_kernel<DT, MODE, MAXB>), dim3((unsigned)blocks), dim3(kFlatWg), 0, st, b);
+    hipLaunchKernelGGL((nf4_flat_kernel<DT, MODE, MAXB>), dim3(L.grid), dim3(L.block), 0, st, b);
 }
 
-// Launch one flat batch.  Tile offsets are (re)computed here for the tile size of
-// the dtype; callers only fill the per-matrix descriptors.  cfg: grid cap
-// (blocks_per_cu), validated by the caller.
-template <int MAXB>
-int launch_flat_batch(const Batch<MAXB>& bt, int dtype, int mode, const nf4_launch_cfg& cfg, hipStream_t st) {
-    if (bt.count == 0) return NF4DQ_OK;
-    const uint32_t tb = 64u * (dtype == NF4DQ_F32 ? 2u : 4u) * kU;
-    Batch<MAXB> b = bt;
-    uint32_t acc = 0;
-    for (uint32_t i = 0; i < b.count; ++i) {
-        b.d[i].tile_begin = acc;
-        acc += (b.d[i].nbytes + tb - 1u) / tb;
-    }
-    b.total_tiles = acc;
-    if (acc == 0) return NF4DQ_OK;
-    uint64_t blocks = (acc + kFlatWaves - 1) / kFlatWaves;
-    // nf4_flat1_kernel for the default grid only: a call that names a cap (nf4_dequant_ref_cfg)
-    // keeps nf4_flat_kernel whether or not the cap binds, so tuning runs and the tests have
-    // the loop kernel to compare against at any size
-    const bool one_tile = cfg.blocks_per_cu <= 0;
-    if (cfg.blocks_per_cu > 0) {
-        const uint64_t cap = (uint64_t)cfg.blocks_per_cu * (uint64_t)cu_count();
-        if (blocks > cap) blocks = cap;
-    }
-#if NF4_FLAT_STAMPS
-    b.stamps = g_stamps;
-#endif
-#define NF4_D(DT_)                                                                        \
-    do {                                                                                  \
-        switch (mode) {                                                                   \
-            case kRef: launch_one<DT_, kRef, MAXB>(b, blocks, one_tile, st); break;       \
-            case kSingle: launch_one<DT_, kSingle, MAXB>(b, blocks, one_tile, st); break; \
-            case kBnb: launch_one<DT_, kBnb, MAXB>(b, blocks, one_tile, st); break;       \
-            default: launch_one<DT_, kBnbSingle, MAXB>(b, blocks, one_tile, st); break;   \
-        }                                                                                 \
-    } while (0)
-    if (dtype == NF4DQ_BF16) NF4_D(NF4DQ_BF16);
-    else if (dtype == NF4DQ_F16) NF4_D(NF4DQ_F16);
-    else NF4_D(NF4DQ_F32);
-#undef NF4_D
-    return hip_rc(hipGetLastError());
-}
-
-inline unsigned rows_grid(int64_t work) {
-    int64_t b = (work + kWg - 1) / kWg;
-    if (b > 65536) b = 65536;  // grid-stride beyond this
-    if (b < 1) b = 1;
-    return (unsigned)b;
-}
-
-// Validation shared by the reference-semantics entry points (mirrors what the
-// reference's .view(m, -1) and slicing accept, kernel_optimized.py:229, :288-312).
-int check_common(const uint8_t* packed, int64_t packed_len, const void* out, int32_t dtype, int64_t m, int64_t n) {
-    if (!valid_dtype(dtype)) return NF4DQ_ERR_ARG;
-    if (m < 0 || n < 0 || packed_len < 0) return NF4DQ_ERR_ARG;
-    if (m == 0 || n == 0) return NF4DQ_OK;
-    if (!packed || !out) return NF4DQ_ERR_ARG;
-    if (packed_len % m) return NF4DQ_ERR_SHAPE;
-    if (packed_len / m < (n + 1) / 2) return NF4DQ_ERR_SHAPE;
-    return NF4DQ_OK;
-}
-
-// Fill a flat-path descriptor for reference / single semantics, or return false
-// when the matrix needs the rows kernel.
-// Buffer descriptors address < 4 GiB: a flat piece holds < 2^29 packed bytes
-// (2 GiB of 16-bit / 4 GiB of fp32 output).  Bigger matrices (a 70B model's
-// 128256 x 8192 lm_head) go as several row-aligned pieces of one launch, each
-// carrying its first scale block (Desc::blk_base); block indices stay < 2^31.
-constexpr int64_t kPieceBytes = int64_t(1) << 29;
-constexpr int64_t kMaxFlatBlocks = int64_t(1) << 31;
-
-bool flat_eligible(const uint8_t* packed, int64_t packed_len, const void* out, int64_t m, int64_t n) {
-    return n % 64 == 0 && packed_len == m * (n / 2) && n / 2 < kPieceBytes && packed_len / 32 < kMaxFlatBlocks &&
-           aligned(packed, 4) && aligned(out, 16);
-}
-
-// Rows per piece of a flat-eligible matrix with n columns.
-inline int64_t piece_rows(int64_t n) { return (kPieceBytes - 1) / (n / 2); }
-
-// Append the row pieces of one flat-eligible matrix (descriptor `proto` covers
-// the whole matrix) to batch `b`, launching whenever it fills.
-template <int MAXB>
-int append_pieces(Batch<MAXB>& b, const Desc& proto, int64_t m, int64_t n, int32_t dtype, int mode,
-                  hipStream_t st) {
-    const int64_t rows = piece_rows(n);
-    const int64_t ob = dtype == NF4DQ_F32 ? 4 * n : 2 * n;
-    for (int64_t r0 = 0; r0 < m; r0 += rows) {
-        const int64_t r1 = r0 + rows < m ? r0 + rows : m;
-        Desc d = proto;
-        d.packed = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(proto.packed) + r0 * (n / 2));
-        d.out = reinterpret_cast<u32x4*>(reinterpret_cast<uint8_t*>(proto.out) + r0 * ob);
-        d.nbytes = (uint32_t)((r1 - r0) * (n / 2));
-        d.blk_base = (uint32_t)(r0 * (n / 64));
-        d.tile_begin = b.total_tiles;
-        b.d[b.count++] = d;
-        b.total_tiles += (d.nbytes + 1023u) / 1024u;
-        if (b.count == (uint32_t)MAXB || b.total_tiles > (1u << 30)) {
-            const int rc = launch_flat_batch(b, dtype, mode, kDefaultCfg, st);
-            if (rc) return rc;
-            b.count = 0;
-            b.total_tiles = 0;
+// One launch of a plan.  Reference / single semantics only reach the chunk, piece and rows
+// kernels; the flat kernels have all four modes.
+int run(const Launch& L, hipStream_t st) {
+    const dim3 g(L.grid), blk(L.block);
+    with_const<NF4DQ_BF16, NF4DQ_F16, NF4DQ_F32>(L.dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if (L.family == kFlat1 || L.family == kFlat) {
+            with_const<kRef, kSingle, kBnb, kBnbSingle>(L.mode, [&](auto md) {
+                if (L.p0 == 1) run_flat<DT, decltype(md)::value, 1>(L, st);
+                else run_flat<DT, decltype(md)::value, NF4DQ_BATCH_MAX>(L, st);
+            });
+        } else if (L.family == kBnbBytes) {
+            hipLaunchKernelGGL((nf4_bnb_bytes_kernel<DT>), g, blk, 0, st, L.as<BnbBytesArgs>());
+        } else {
+            with_const<kRef, kSingle>(L.mode, [&](auto md) {
+                constexpr int MODE = decltype(md)::value;
+                if (L.family == kRows) {
+                    hipLaunchKernelGGL((nf4_rows_kernel<DT, MODE>), g, blk, 0, st, L.as<RowsArgs>());
+                } else if (L.family == kChunkDense) {
+                    if constexpr (DT != NF4DQ_F32)
+                        hipLaunchKernelGGL((nf4_chunk_dense_kernel<DT, MODE>), g, blk, 0, st, L.as<ChunkArgs>());
+                } else if (L.family == kChunk) {
+                    with_const<4, 1>(L.p0, [&](auto lw) {
+                        with_const<16, 4>(L.p1, [&](auto sw) {
+                            hipLaunchKernelGGL((nf4_chunk_kernel<DT, MODE, decltype(lw)::value, decltype(sw)::value>), g,
+                                               blk, 0, st, L.as<ChunkArgs>());
+                        });
+                    });
+                } else {
+                    with_const<2, 1, 0>(L.p0, [&](auto re) {
+                        with_const<1, 0>(L.p1, [&](auto tri) {
+                            constexpr int RE = decltype(re)::value;
+                            constexpr bool TRI = decltype(tri)::value != 0;
+                            if constexpr (DT == NF4DQ_F32)
+                                hipLaunchKernelGGL((nf4_piece32_kernel<MODE, RE, TRI>), g, blk, 0, st, L.as<PieceArgs>());
+                            else
+                                hipLaunchKernelGGL((nf4_piece_kernel<DT, MODE, RE, TRI>), g, blk, 0, st,
+                                                   L.as<PieceArgs>());
+                        });
+                    });
+                }
+            });
         }
-    }
-    return NF4DQ_OK;
-}
-
-// One flat-eligible matrix: a single-descriptor launch, or pieces.
-int launch_flat_matrix(const Desc& proto, int64_t m, int64_t n, int32_t dtype, int mode, const nf4_launch_cfg& cfg,
-                       hipStream_t st) {
-    const int64_t packed_len = m * (n / 2);
-    if (packed_len < kPieceBytes) {
-        Batch<1> b{};
-        b.d[0] = proto;
-        b.d[0].nbytes = (uint32_t)packed_len;
-        b.count = 1;
-        b.total_tiles = (uint32_t)((packed_len + 1023) / 1024);
-        return launch_flat_batch(b, dtype, mode, cfg, st);
-    }
-    Batch<NF4DQ_BATCH_MAX> b{};
-    const int rc = append_pieces(b, proto, m, n, dtype, mode, st);
-    if (rc || b.count == 0) return rc;
-    return launch_flat_batch(b, dtype, mode, kDefaultCfg, st);
-}
-
-Desc ref_desc(const uint8_t* packed, int64_t packed_len, const uint8_t* a1, int64_t nb, const float* a2,
-              int64_t n2, void* out, int64_t n) {
-    Desc d{};
-    d.packed = reinterpret_cast<const uint32_t*>(packed);
-    d.a1 = a1;
-    d.a2 = a2;
-    d.out = reinterpret_cast<u32x4*>(out);
-    d.nbytes = packed_len < kPieceBytes ? (uint32_t)packed_len : 0u;  // pieces set their own
-    const int64_t bpr = (n + 63) / 64;
-    d.groups = (uint32_t)((bpr + 3) / 4);
-    // moduli above 2^31 never wrap for indices < 2^31: clamp keeps FastDiv valid
-    d.nb = make_fastdiv((uint32_t)(nb > (int64_t(1) << 31) ? (int64_t(1) << 31) : nb));
-    d.n2 = make_fastdiv((uint32_t)(n2 > (int64_t(1) << 31) ? (int64_t(1) << 31) : n2));
-    d.bpr = make_fastdiv((uint32_t)bpr);
-    d.blk_shift = 5;  // 64 elements = 32 packed bytes
-    return d;
-}
-
-// Fill the chunk kernel's shape fields, or return false when the matrix is past its
-// limits: every index it forms is 32-bit (chunks, blocks, scale indices, offsets within
-// the rows one wave's 256 chunks touch) and its stores need element-aligned output.
-bool chunk_args(ChunkArgs& A, const uint8_t* packed, int64_t packed_len, void* out, int32_t dtype, int64_t m,
-                int64_t n) {
-    const int64_t stride = packed_len / m;
-    const int64_t L = ((n + 1) / 2 + 3) / 4;
-    const int64_t bpr = (n + 63) / 64;
-    const int64_t ob = dtype == NF4DQ_F32 ? 4 : 2;
-    const int64_t span = 256 / L + 2;  // rows one wave touches, at most
-    const int64_t lim = int64_t(1) << 31;
-    if (m * L >= lim - 1024 || m * bpr >= lim || n >= (int64_t(1) << 28) || span * stride >= lim ||
-        span * n * ob >= lim || !aligned(out, (uintptr_t)ob))
-        return false;
-    A.packed = packed;
-    A.out = out;
-    A.packed_len = (uint64_t)packed_len;
-    A.out_elems = (uint64_t)(m * n);
-    A.stride = (uint32_t)stride;
-    A.n = (uint32_t)n;
-    A.chunks = (uint32_t)(m * L);
-    A.L = make_fastdiv((uint32_t)L);
-    A.bpr = make_fastdiv((uint32_t)bpr);
-    A.groups = (uint32_t)((bpr + 3) / 4);
-    return true;
-}
-
-template <int DT, int MODE, int LW>
-void launch_chunks_lw(const ChunkArgs& A, int sw, unsigned g, hipStream_t st) {
-    if (sw == 16) hipLaunchKernelGGL((nf4_chunk_kernel<DT, MODE, LW, 16>), dim3(g), dim3(kWg), 0, st, A);
-    else hipLaunchKernelGGL((nf4_chunk_kernel<DT, MODE, LW, 4>), dim3(g), dim3(kWg), 0, st, A);
-}
-
-// The dense form's shapes (checked first).
-bool dense_eligible(const ChunkArgs& A, int32_t dtype) {
-    return dtype != NF4DQ_F32 && A.L.d >= 64u && A.stride == 4u * A.L.d && A.n % 8u == 0 && aligned(A.packed, 4) &&
-           aligned(A.out, 16) && A.chunks < (1u << 27);
-}
-
-// The piece kernels' shapes: rows of >= 512 elements (a step then crosses at most one row end)
-// the dense form does not take (16-bit output: n % 8 != 0, padded rows, the output off
-// 16-byte alignment or the packed weight off 4-byte alignment; fp32: every such shape), and
-// offsets below 2^31.
-bool piece_eligible(const ChunkArgs& A, int32_t dtype) {
-    const uint64_t half = (A.n + 1u) / 2u;
-    const uint64_t rows = A.out_elems / A.n;
-    const uint64_t ob = dtype == NF4DQ_F32 ? 4u : 2u;
-    // (padded 16-bit rows the chunk kernel stores whole, n % 8 == 0 and an aligned output,
-    // stay there: the same time, two loads fewer per piece; profiles/r06/chunk/s22)
-    if (A.stride != half && dtype != NF4DQ_F32 && A.n % 8u == 0 && aligned(A.out, 16)) return false;
-    return A.stride >= half && A.packed_len == rows * A.stride && A.n >= 512u &&
-           ob * (A.out_elems + 64u) < (uint64_t(1) << 31) && A.packed_len + 8u < (uint64_t(1) << 31);
-}
-
-template <int MODE, int DT, int RE, bool TRI>
-void launch_pieces_k(const PieceArgs& P, unsigned g, hipStream_t st) {
-    if constexpr (DT == NF4DQ_F32) hipLaunchKernelGGL((nf4_piece32_kernel<MODE, RE, TRI>), dim3(g), dim3(kWg), 0, st, P);
-    else hipLaunchKernelGGL((nf4_piece_kernel<DT, MODE, RE, TRI>), dim3(g), dim3(kWg), 0, st, P);
-}
-
-template <int MODE, int DT, int RE>
-void launch_pieces_re(const PieceArgs& P, unsigned g, hipStream_t st) {
-    // TRI: the last block of a row is shorter than a piece (a piece can hold three blocks)
-    const uint32_t tail = P.n % 64u;
-    if (tail != 0u && tail < (DT == NF4DQ_F32 ? 4u : 8u)) launch_pieces_k<MODE, DT, RE, true>(P, g, st);
-    else launch_pieces_k<MODE, DT, RE, false>(P, g, st);
-}
-
-template <int MODE, int DT>
-void launch_pieces_dt(const PieceArgs& P, unsigned g, hipStream_t st) {
-    if (P.stride != P.half) launch_pieces_re<MODE, DT, 2>(P, g, st);  // padded rows
-    else if (P.n & 1u) launch_pieces_re<MODE, DT, 1>(P, g, st);
-    else launch_pieces_re<MODE, DT, 0>(P, g, st);
-}
-
-template <int MODE>
-int launch_pieces(const ChunkArgs& A, int32_t dtype, hipStream_t st) {
-    PieceArgs P{};
-    const uint32_t ob = dtype == NF4DQ_F32 ? 4u : 2u, per = 16u / ob;  // output bytes, elements per piece
-    const uintptr_t pw = (uintptr_t)A.packed, ow = (uintptr_t)A.out;
-    P.packed = reinterpret_cast<const uint8_t*>(pw & ~uintptr_t(3));
-    P.kb = (uint32_t)(pw & 3u);
-    P.prange = (uint32_t)((P.kb + A.packed_len + 3u) & ~uint64_t(3));
-    P.a1 = A.a1;
-    P.a2 = A.a2;
-    P.out = A.out;
-    P.line = reinterpret_cast<void*>(ow & ~uintptr_t(127));
-    P.sa = (uint32_t)((ow & 127u) / ob);
-    P.elems = (uint32_t)A.out_elems;
-    P.n = A.n;
-    P.half = (A.n + 1u) / 2u;
-    P.stride = A.stride;
-    P.nf = make_fastdiv(A.n);
-    P.bpr = A.bpr;
-    P.groups = A.groups;
-    P.nb = A.nb;
-    P.n2 = A.n2;
-    P.rs = A.rs;
-    const uint32_t pieces = (P.sa + P.elems + per - 1u) / per;
-    const unsigned g = (pieces + 1023u) / 1024u;  // 4 waves x 256 pieces
-    if (dtype == NF4DQ_BF16) launch_pieces_dt<MODE, NF4DQ_BF16>(P, g, st);
-    else if (dtype == NF4DQ_F16) launch_pieces_dt<MODE, NF4DQ_F16>(P, g, st);
-    else launch_pieces_dt<MODE, NF4DQ_F32>(P, g, st);
+    });
     return hip_rc(hipGetLastError());
 }
 
-template <int MODE>
-int launch_chunks(const ChunkArgs& A, int32_t dtype, hipStream_t st) {
-    const unsigned g = (unsigned)((A.chunks + 1023u) / 1024u);  // 4 waves x 256 chunks
-    if (!dense_eligible(A, dtype) && piece_eligible(A, dtype)) return launch_pieces<MODE>(A, dtype, st);
-    if (dense_eligible(A, dtype)) {
-        if (dtype == NF4DQ_BF16) hipLaunchKernelGGL((nf4_chunk_dense_kernel<NF4DQ_BF16, MODE>), dim3(g), dim3(kWg), 0, st, A);
-        else hipLaunchKernelGGL((nf4_chunk_dense_kernel<NF4DQ_F16, MODE>), dim3(g), dim3(kWg), 0, st, A);
-        return hip_rc(hipGetLastError());
-    }
-    const int lw = aligned(A.packed, 4) && A.stride % 4 == 0 ? 4 : 1;
-    int sw;
-    if (dtype == NF4DQ_F32) sw = A.n % 4 == 0 && aligned(A.out, 16) ? 16 : 4;
-    else sw = A.n % 8 == 0 && aligned(A.out, 16) ? 16 : 4;  // (4: staged through LDS)
-#define NF4_C(DT_)                                                                 \
-    do {                                                                           \
-        if (lw == 4) launch_chunks_lw<DT_, MODE, 4>(A, sw, g, st);                 \
-        else launch_chunks_lw<DT_, MODE, 1>(A, sw, g, st);                         \
-    } while (0)
-    if (dtype == NF4DQ_BF16) NF4_C(NF4DQ_BF16);
-    else if (dtype == NF4DQ_F16) NF4_C(NF4DQ_F16);
-    else NF4_C(NF4DQ_F32);
-#undef NF4_C
-    return hip_rc(hipGetLastError());
-}
-
-inline FastDiv clamped_fastdiv(int64_t d) {  // moduli above 2^31 never wrap for indices < 2^31
-    return make_fastdiv((uint32_t)(d > (int64_t(1) << 31) ? (int64_t(1) << 31) : d));
-}
-
-int ref_impl(const uint8_t* packed, int64_t packed_len, const uint8_t* a1, int64_t nb, const float* a2, int64_t n2,
-             void* out, int32_t dtype, int64_t m, int64_t n, const nf4_launch_cfg& cfg, hipStream_t st) {
-    int rc = check_common(packed, packed_len, out, dtype, m, n);
-    if (rc || m == 0 || n == 0) return rc;
-    if (!a1 || !a2 || nb <= 0 || n2 <= 0) return NF4DQ_ERR_ARG;
-    const bool rows_only = cfg.flags & NF4DQ_CFG_ROWS, chunks = cfg.flags & NF4DQ_CFG_CHUNKS;
-    if (!rows_only && !chunks && flat_eligible(packed, packed_len, out, m, n))
-        return launch_flat_matrix(ref_desc(packed, packed_len, a1, nb, a2, n2, out, n), m, n, dtype, kRef, cfg, st);
-    ChunkArgs C{};
-    if (!rows_only && chunk_args(C, packed, packed_len, out, dtype, m, n)) {
-        C.a1 = a1;
-        C.a2 = a2;
-        C.nb = clamped_fastdiv(nb);
-        C.n2 = clamped_fastdiv(n2);
-        return launch_chunks<kRef>(C, dtype, st);
-    }
-    RowsArgs A{};
-    A.packed = packed;
-    A.a1 = a1;
-    A.a2 = a2;
-    A.out = out;
-    A.m = m;
-    A.n = n;
-    A.stride = packed_len / m;
-    A.cols_b = (n + 1) / 2;
-    A.nb = nb;
-    A.n2 = n2;
-    A.bpr = (n + 63) / 64;
-    A.groups = (A.bpr + 3) / 4;
-    const unsigned g = rows_grid(m * A.cols_b);
-    if (dtype == NF4DQ_BF16) hipLaunchKernelGGL((nf4_rows_kernel<NF4DQ_BF16, kRef>), dim3(g), dim3(kWg), 0, st, A);
-    else if (dtype == NF4DQ_F16) hipLaunchKernelGGL((nf4_rows_kernel<NF4DQ_F16, kRef>), dim3(g), dim3(kWg), 0, st, A);
-    else hipLaunchKernelGGL((nf4_rows_kernel<NF4DQ_F32, kRef>), dim3(g), dim3(kWg), 0, st, A);
-    return hip_rc(hipGetLastError());
-}
+struct OnStream {  // the plan's sink: every launch goes out on the call's stream
+    hipStream_t st;
+    int operator()(const Launch& L) const { return run(L, st); }
+};
 
 }  // namespace
 
@@ -1857,178 +1491,44 @@ extern "C" {
 int nf4_dequant_ref(const uint8_t* packed, int64_t packed_len, const uint8_t* absmax_q, int64_t nb,
                     const float* absmax2, int64_t n2, void* out, int32_t out_dtype, int64_t m, int64_t n,
                     void* hip_stream) {
-    return ref_impl(packed, packed_len, absmax_q, nb, absmax2, n2, out, out_dtype, m, n, kDefaultCfg,
-                    reinterpret_cast<hipStream_t>(hip_stream));
+    OnStream emit{reinterpret_cast<hipStream_t>(hip_stream)};
+    return plan_ref(packed, packed_len, absmax_q, nb, absmax2, n2, out, out_dtype, m, n, kDefaultCfg, 0, emit);
 }
 
 int nf4_dequant_ref_cfg(const uint8_t* packed, int64_t packed_len, const uint8_t* absmax_q, int64_t nb,
                         const float* absmax2, int64_t n2, void* out, int32_t out_dtype, int64_t m, int64_t n,
                         const nf4_launch_cfg* cfg, void* hip_stream) {
-    nf4_launch_cfg c = cfg ? *cfg : kDefaultCfg;
-    if (c.tile_dwords != 4 || c.nontemporal != 1 || c.blocks_per_cu < 0) return NF4DQ_ERR_ARG;
-    if (c.flags & ~(NF4DQ_CFG_ROWS | NF4DQ_CFG_CHUNKS)) return NF4DQ_ERR_ARG;
-    if ((c.flags & NF4DQ_CFG_ROWS) && (c.flags & NF4DQ_CFG_CHUNKS)) return NF4DQ_ERR_ARG;
-    return ref_impl(packed, packed_len, absmax_q, nb, absmax2, n2, out, out_dtype, m, n, c,
-                    reinterpret_cast<hipStream_t>(hip_stream));
+    OnStream emit{reinterpret_cast<hipStream_t>(hip_stream)};
+    nf4_launch_cfg c;
+    if (const int rc = check_cfg(cfg, c)) return rc;
+    // (the CU count only caps a grid that names blocks_per_cu)
+    return plan_ref(packed, packed_len, absmax_q, nb, absmax2, n2, out, out_dtype, m, n, c,
+                    c.blocks_per_cu > 0 ? cu_count() : 0, emit);
 }
 
 int nf4_dequant_single(const uint8_t* packed, int64_t packed_len, const float* absmax, int64_t absmax_len,
                        void* out, int32_t out_dtype, int64_t m, int64_t n, void* hip_stream) {
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    int rc = check_common(packed, packed_len, out, out_dtype, m, n);
-    if (rc || m == 0 || n == 0) return rc;
-    if (!absmax || absmax_len < 0) return NF4DQ_ERR_ARG;
-    const int64_t bpr = (n + 63) / 64;
-    if (absmax_len % m || absmax_len / m < bpr) return NF4DQ_ERR_SHAPE;
-    const int64_t rs = absmax_len / m;
-    if (flat_eligible(packed, packed_len, out, m, n) && absmax_len < (int64_t(1) << 31)) {
-        Desc d = ref_desc(packed, packed_len, nullptr, 1, absmax, 1, out, n);
-        d.n2 = make_fastdiv((uint32_t)rs);
-        return launch_flat_matrix(d, m, n, out_dtype, kSingle, kDefaultCfg, st);
-    }
-    ChunkArgs C{};
-    if (m * rs < (int64_t(1) << 31) && chunk_args(C, packed, packed_len, out, out_dtype, m, n)) {
-        C.a2 = absmax;
-        C.rs = (uint32_t)rs;
-        return launch_chunks<kSingle>(C, out_dtype, st);
-    }
-    RowsArgs A{};
-    A.packed = packed;
-    A.a2 = absmax;
-    A.out = out;
-    A.m = m;
-    A.n = n;
-    A.stride = packed_len / m;
-    A.cols_b = (n + 1) / 2;
-    A.bpr = bpr;
-    A.rs = rs;
-    const unsigned g = rows_grid(m * A.cols_b);
-    if (out_dtype == NF4DQ_BF16) hipLaunchKernelGGL((nf4_rows_kernel<NF4DQ_BF16, kSingle>), dim3(g), dim3(kWg), 0, st, A);
-    else if (out_dtype == NF4DQ_F16) hipLaunchKernelGGL((nf4_rows_kernel<NF4DQ_F16, kSingle>), dim3(g), dim3(kWg), 0, st, A);
-    else hipLaunchKernelGGL((nf4_rows_kernel<NF4DQ_F32, kSingle>), dim3(g), dim3(kWg), 0, st, A);
-    return hip_rc(hipGetLastError());
+    OnStream emit{reinterpret_cast<hipStream_t>(hip_stream)};
+    return plan_single(packed, packed_len, absmax, absmax_len, out, out_dtype, m, n, emit);
 }
 
 int nf4_dequant_ref_batched(const nf4_matrix_desc* descs, int32_t count, int32_t out_dtype, void* hip_stream) {
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    if (count < 0 || (count > 0 && !descs)) return NF4DQ_ERR_ARG;
-    if (!valid_dtype(out_dtype)) return NF4DQ_ERR_ARG;
-    // Validate everything before launching anything.
-    for (int32_t i = 0; i < count; ++i) {
-        const nf4_matrix_desc& d = descs[i];
-        int rc = check_common(d.packed, d.packed_len, d.out, out_dtype, d.m, d.n);
-        if (rc) return rc;
-        if (d.m == 0 || d.n == 0) continue;
-        if (!d.absmax_q || !d.absmax2 || d.nb <= 0 || d.n2 <= 0) return NF4DQ_ERR_ARG;
-    }
-    Batch<NF4DQ_BATCH_MAX> b{};
-    b.count = 0;
-    b.total_tiles = 0;
-    for (int32_t i = 0; i < count; ++i) {
-        const nf4_matrix_desc& d = descs[i];
-        if (d.m == 0 || d.n == 0) continue;
-        if (!flat_eligible(d.packed, d.packed_len, d.out, d.m, d.n)) {
-            int rc = ref_impl(d.packed, d.packed_len, d.absmax_q, d.nb, d.absmax2, d.n2, d.out, out_dtype, d.m, d.n,
-                              kDefaultCfg, st);
-            if (rc) return rc;
-            continue;
-        }
-        const int rc = append_pieces(b, ref_desc(d.packed, d.packed_len, d.absmax_q, d.nb, d.absmax2, d.n2, d.out,
-                                                 d.n), d.m, d.n, out_dtype, kRef, st);
-        if (rc) return rc;
-    }
-    if (b.count) return launch_flat_batch(b, out_dtype, kRef, kDefaultCfg, st);
-    return NF4DQ_OK;
-}
-
-static int bnb_common(const uint8_t* packed, const uint8_t* a1, int64_t nb, const float* code2, const float* a2,
-                      int64_t n2, float offset, void* out, int32_t dtype, int64_t numel, int32_t blocksize,
-                      int32_t blocksize2, bool single, hipStream_t st) {
-    if (!valid_dtype(dtype)) return NF4DQ_ERR_ARG;
-    if (numel < 0) return NF4DQ_ERR_ARG;
-    if (numel == 0) return NF4DQ_OK;
-    if (!packed || !out || !a2) return NF4DQ_ERR_ARG;
-    if (blocksize < 64 || (blocksize & (blocksize - 1))) return NF4DQ_ERR_ARG;
-    const int64_t nblk = (numel + blocksize - 1) / blocksize;
-    if (nb < nblk) return NF4DQ_ERR_SHAPE;
-    if (!single) {
-        if (!a1 || !code2) return NF4DQ_ERR_ARG;
-        if (blocksize2 <= 0 || (blocksize2 & (blocksize2 - 1))) return NF4DQ_ERR_ARG;
-        if (n2 < (nblk + blocksize2 - 1) / blocksize2) return NF4DQ_ERR_SHAPE;
-    }
-    const int mode = single ? kBnbSingle : kBnb;
-    if (numel % 8 == 0 && nblk < kMaxFlatBlocks && blocksize <= (1 << 28) && aligned(packed, 4) && aligned(out, 16)) {
-        // the stream as one matrix of rows of kPieceBytes / 2 packed bytes (a
-        // multiple of every block's byte count): pieces exactly as above
-        const int64_t nbytes = numel / 2;
-        const int64_t row = nbytes < kPieceBytes ? nbytes : kPieceBytes / 2;
-        Desc d{};
-        d.packed = reinterpret_cast<const uint32_t*>(packed);
-        d.a1 = a1;
-        d.a2 = a2;
-        d.code2 = code2;
-        d.out = reinterpret_cast<u32x4*>(out);
-        d.offset = offset;
-        d.blk_shift = (uint32_t)ilog2((uint64_t)blocksize / 2);
-        d.blk2_shift = single ? 0u : (uint32_t)ilog2((uint64_t)blocksize2);
-        if (nbytes < kPieceBytes) {
-            Batch<1> b{};
-            b.d[0] = d;
-            b.d[0].nbytes = (uint32_t)nbytes;
-            b.count = 1;
-            b.total_tiles = (uint32_t)((nbytes + 1023) / 1024);
-            return launch_flat_batch(b, dtype, mode, kDefaultCfg, st);
-        }
-        Batch<NF4DQ_BATCH_MAX> b{};
-        const int64_t ob = dtype == NF4DQ_F32 ? 8 : 4;  // output bytes per packed byte
-        for (int64_t p0 = 0; p0 < nbytes; p0 += row) {
-            Desc x = d;
-            const int64_t len = nbytes - p0 < row ? nbytes - p0 : row;
-            x.packed = reinterpret_cast<const uint32_t*>(packed + p0);
-            x.out = reinterpret_cast<u32x4*>(reinterpret_cast<uint8_t*>(out) + p0 * ob);
-            x.nbytes = (uint32_t)len;
-            x.blk_base = (uint32_t)(p0 >> d.blk_shift);
-            x.tile_begin = b.total_tiles;
-            b.d[b.count++] = x;
-            b.total_tiles += (uint32_t)((len + 1023) / 1024);
-            if (b.count == NF4DQ_BATCH_MAX) {
-                const int rc = launch_flat_batch(b, dtype, mode, kDefaultCfg, st);
-                if (rc) return rc;
-                b.count = 0;
-                b.total_tiles = 0;
-            }
-        }
-        return b.count ? launch_flat_batch(b, dtype, mode, kDefaultCfg, st) : NF4DQ_OK;
-    }
-    BnbBytesArgs A{};
-    A.packed = packed;
-    A.a1 = a1;
-    A.code2 = code2;
-    A.a2 = a2;
-    A.out = out;
-    A.offset = offset;
-    A.numel = numel;
-    A.blk_shift_elems = ilog2((uint64_t)blocksize);
-    A.blk2_shift = single ? 0 : ilog2((uint64_t)blocksize2);
-    A.single = single ? 1 : 0;
-    const unsigned g = rows_grid((numel + 1) / 2);
-    if (dtype == NF4DQ_BF16) hipLaunchKernelGGL((nf4_bnb_bytes_kernel<NF4DQ_BF16>), dim3(g), dim3(kWg), 0, st, A);
-    else if (dtype == NF4DQ_F16) hipLaunchKernelGGL((nf4_bnb_bytes_kernel<NF4DQ_F16>), dim3(g), dim3(kWg), 0, st, A);
-    else hipLaunchKernelGGL((nf4_bnb_bytes_kernel<NF4DQ_F32>), dim3(g), dim3(kWg), 0, st, A);
-    return hip_rc(hipGetLastError());
+    OnStream emit{reinterpret_cast<hipStream_t>(hip_stream)};
+    return plan_ref_batched(descs, count, out_dtype, emit);
 }
 
 int nf4_dequant_bnb(const uint8_t* packed, const uint8_t* absmax_q, int64_t nb, const float* code2,
                     const float* absmax2, int64_t n2, float offset, void* out, int32_t out_dtype, int64_t numel,
                     int32_t blocksize, int32_t blocksize2, void* hip_stream) {
-    return bnb_common(packed, absmax_q, nb, code2, absmax2, n2, offset, out, out_dtype, numel, blocksize, blocksize2,
-                      false, reinterpret_cast<hipStream_t>(hip_stream));
+    OnStream emit{reinterpret_cast<hipStream_t>(hip_stream)};
+    return plan_bnb(packed, absmax_q, nb, code2, absmax2, n2, offset, out, out_dtype, numel, blocksize, blocksize2,
+                    false, emit);
 }
 
 int nf4_dequant_bnb_single(const uint8_t* packed, const float* absmax, int64_t nabs, void* out, int32_t out_dtype,
                            int64_t numel, int32_t blocksize, void* hip_stream) {
-    return bnb_common(packed, nullptr, nabs, nullptr, absmax, 0, 0.0f, out, out_dtype, numel, blocksize, 1, true,
-                      reinterpret_cast<hipStream_t>(hip_stream));
+    OnStream emit{reinterpret_cast<hipStream_t>(hip_stream)};
+    return plan_bnb(packed, nullptr, nabs, nullptr, absmax, 0, 0.0f, out, out_dtype, numel, blocksize, 1, true, emit);
 }
 
 const char* nf4_strerror(int code) {

@@ -1,7 +1,8 @@
 """The chunk and piece kernels (``-m gpu``): every shape the flat kernel does not take.
 
 n % 64 != 0, padded packed rows and unaligned pointers go through the kernels of
-csrc/nf4_dequant.hip.  Which instantiation a shape takes (launch_chunks):
+csrc/nf4_dequant.hip.  Which instantiation a shape takes (plan_chunks in
+csrc/nf4_dequant_plan.h; tests/test_dequant_plan_cpu.py holds CASES below to it):
 * nf4_chunk_dense_kernel -- 16-bit output, n % 8 == 0, packed rows of exactly 4 L bytes
   (L = chunks per row >= 64), 4-byte-aligned packed weight, 16-byte-aligned output;
 * nf4_piece_kernel / nf4_piece32_kernel -- rows of n >= 512 that the dense form does not
@@ -63,58 +64,64 @@ def _ref_call(dev, p, a1, a2, m, n, dt, p_off=0, o_elem_off=0, flags=None):
     return buf, start
 
 
-# (m, n, extra stride bytes, packed byte offset, output element offset): the form each
-# selects for 16-bit output (fp32: the general form, SW 16 when n % 4 == 0 and aligned)
+# (m, n, extra stride bytes, packed byte offset, output element offset, form for 16-bit
+# output, form for fp32 output).  The forms -- "dense", "piece", "piece32", "chunk<LW>.<SW>" --
+# are what the host plan (csrc/nf4_dequant_plan.h) chooses; tests/test_dequant_plan_cpu.py
+# asserts that it does, so a changed predicate cannot silently move a case to another kernel.
 CASES = [
-    (37, 1000, 0, 0, 0),      # n % 8 == 0, rows of exactly 4 L bytes, L >= 64: the dense form
-    (5, 4080, 0, 0, 0),       # (the dense form)
-    (33, 1000, 4, 0, 0),      # padded rows, n % 8 == 0: LW 4, SW 16 (fp32: the piece kernel)
-    (33, 1002, 3, 0, 0),      # padded rows, n % 8 != 0: the piece kernel, next row's bytes loaded apart
-    (33, 504, 4, 0, 0),       # padded rows < 512: LW 4 (dword loads), SW 16 (16-byte chunk stores), L < 64
-    (33, 508, 4, 0, 0),       # LW 4, L >= 64: 16-bit SW 4 (staged), fp32 SW 16
-    (9, 4080, 0, 0, 1),       # output off 16-byte alignment, tight rows: the piece kernel (fp32: LW 4, SW 4)
-    (9, 4080, 4, 0, 1),       # the same with padded rows (piece kernel)
-    (9, 510, 4, 0, 1),        # rows < 512, L >= 64, output off alignment: LW 4, SW 4 (staged)
-    (9, 1002, 0, 0, 0),       # n % 8 == 2, stride 501: the piece kernel (fp32: LW 1, SW 4)
-    (9, 1002, 1, 0, 0),       # n % 8 == 2, padded to stride 502 (piece kernel)
-    (9, 506, 1, 0, 0),        # stride 254, L >= 64: LW 1, SW 4 (staged)
-    (3, 6, 0, 0, 0),          # L = 1: LW 1, SW 4, per-step row division
-    (7, 77, 0, 0, 0),         # odd n (stride 39): LW 1, SW 4
-    (1, 1, 0, 0, 0),
-    (4, 3, 0, 0, 0),
-    (11, 200, 3, 0, 0),       # padded rows, stride % 4 != 0: LW 1, SW 16, L < 64
-    (11, 200, 4, 0, 0),       # padded rows, stride % 4 == 0: LW 4, SW 16, L < 64
-    (6, 256, 2, 0, 0),        # n % 64 == 0 but padded: not flat (LW 1)
-    (6, 256, 0, 1, 0),        # odd packed pointer: LW 1
-    (6, 256, 0, 2, 1),        # output one element off 16-byte alignment: SW 4
-    (10, 1000, 0, 3, 3),      # piece kernel: odd packed address, output 3 elements off
-    (10, 1000, 2, 3, 3),      # the same, padded rows (piece kernel)
-    (10, 510, 2, 3, 3),       # rows < 512: LW 1, SW 4, L >= 64
-    (3000, 2, 0, 0, 0),       # one chunk per row: 256 rows per wave (per-lane scale gathers)
-    (300, 18, 5, 0, 1),
-    (129, 4100, 4, 0, 0),     # padded rows, n % 64 == 4 (piece kernel, three blocks)
-    (129, 509, 1, 0, 0),      # rows < 512, stride 256: LW 4, SW 4, partial last wave
+    (37, 1000, 0, 0, 0, "dense", "piece32"),   # n % 8 == 0, rows of exactly 4 L bytes, L >= 64: the dense form
+    (5, 4080, 0, 0, 0, "dense", "piece32"),
+    (33, 1000, 4, 0, 0, "chunk4.16", "piece32"),  # padded rows, n % 8 == 0: LW 4, SW 16 (fp32: the piece kernel)
+    (33, 1002, 3, 0, 0, "piece", "piece32"),   # padded rows, n % 8 != 0: the piece kernel, next row's bytes loaded apart
+    (33, 504, 4, 0, 0, "chunk4.16", "chunk4.16"),  # padded rows < 512: dword loads, 16-byte chunk stores, L < 64
+    (33, 508, 4, 0, 0, "chunk1.4", "chunk1.16"),   # stride 258, L >= 64: LW 1; 16-bit SW 4 (staged), fp32 SW 16
+    (9, 4080, 0, 0, 1, "piece", "piece32"),    # output off 16-byte alignment, tight rows: the piece kernels
+    (9, 4080, 4, 0, 1, "piece", "piece32"),    # the same with padded rows
+    (9, 510, 4, 0, 1, "chunk1.4", "chunk1.4"),  # rows < 512, stride 259, L >= 64, output off alignment: LW 1, SW 4
+    (9, 1002, 0, 0, 0, "piece", "piece32"),    # n % 8 == 2, stride 501: the piece kernels
+    (9, 1002, 1, 0, 0, "piece", "piece32"),    # n % 8 == 2, padded to stride 502
+    (9, 506, 1, 0, 0, "chunk1.4", "chunk1.4"),  # stride 254, L >= 64: LW 1, SW 4 (staged)
+    (3, 6, 0, 0, 0, "chunk1.4", "chunk1.4"),   # L = 1: LW 1, SW 4, per-step row division
+    (7, 77, 0, 0, 0, "chunk1.4", "chunk1.4"),  # odd n (stride 39): LW 1, SW 4
+    (1, 1, 0, 0, 0, "chunk1.4", "chunk1.4"),
+    (4, 3, 0, 0, 0, "chunk1.4", "chunk1.4"),
+    (11, 200, 3, 0, 0, "chunk1.16", "chunk1.16"),  # padded rows, stride % 4 != 0: LW 1, SW 16, L < 64
+    (11, 200, 4, 0, 0, "chunk4.16", "chunk4.16"),  # padded rows, stride % 4 == 0: LW 4, SW 16, L < 64
+    (6, 256, 2, 0, 0, "chunk1.16", "chunk1.16"),   # n % 64 == 0 but padded: not flat (LW 1)
+    (6, 256, 0, 1, 0, "chunk1.16", "chunk1.16"),   # odd packed pointer: LW 1
+    (6, 256, 0, 2, 1, "chunk1.4", "chunk1.4"),     # output one element off 16-byte alignment: SW 4
+    (10, 1000, 0, 3, 3, "piece", "piece32"),   # piece kernel: odd packed address, output 3 elements off
+    (10, 1000, 2, 3, 3, "piece", "piece32"),   # the same, padded rows
+    (10, 510, 2, 3, 3, "chunk1.4", "chunk1.4"),  # rows < 512: LW 1, SW 4, L >= 64
+    (3000, 2, 0, 0, 0, "chunk1.4", "chunk1.4"),  # one chunk per row: 256 rows per wave (per-lane scale gathers)
+    (300, 18, 5, 0, 1, "chunk1.4", "chunk1.4"),
+    (129, 4100, 4, 0, 0, "piece", "piece32"),  # padded rows, n % 64 == 4 (three blocks in a 16-bit piece)
+    (129, 509, 1, 0, 0, "chunk4.4", "chunk4.4"),  # rows < 512, stride 256: LW 4, SW 4, partial last wave
     # the piece kernel: even n (the stream runs across row ends), odd n (a pad nibble per
     # row), the shortest last block it takes (8: n % 64 == 8), n % 64 == 0 with the output
     # off alignment, output offsets up to 63 elements into the first line, one row
-    (9, 4090, 0, 0, 0),
-    (9, 4095, 0, 0, 0),
-    (7, 1007, 0, 1, 37),
-    (5, 520, 0, 2, 63),
-    (6, 4096, 0, 3, 5),
-    (1, 600, 0, 0, 9),
-    (70, 521, 0, 0, 0),       # rows of 521 (last block of 9): a step crosses a row end in most lanes
-    (9, 4096, 0, 1, 0),       # n % 64 == 0, aligned output, odd packed address
+    (9, 4090, 0, 0, 0, "piece", "piece32"),
+    (9, 4095, 0, 0, 0, "piece", "piece32"),
+    (7, 1007, 0, 1, 37, "piece", "piece32"),
+    (5, 520, 0, 2, 63, "piece", "piece32"),
+    (6, 4096, 0, 3, 5, "piece", "piece32"),
+    (1, 600, 0, 0, 9, "piece", "piece32"),
+    (70, 521, 0, 0, 0, "piece", "piece32"),    # rows of 521 (last block of 9): a step crosses a row end in most lanes
+    (9, 4096, 0, 1, 0, "piece", "piece32"),    # n % 64 == 0, aligned output, odd packed address
     # rows whose last block is shorter than a piece (three blocks in one piece)
-    (129, 4100, 0, 0, 0),
-    (9, 4097, 0, 1, 3),
-    (5, 577, 0, 2, 17),
-    (8, 515, 0, 3, 1),
+    (129, 4100, 0, 0, 0, "piece", "piece32"),
+    (9, 4097, 0, 1, 3, "piece", "piece32"),
+    (5, 577, 0, 2, 17, "piece", "piece32"),
+    (8, 515, 0, 3, 1, "piece", "piece32"),
+    # dword loads with the staged store and rows of >= 64 chunks: what (33, 508, 4) and
+    # (9, 510, 4, 0, 1) above were once labelled as, but their strides are no multiple of 4
+    (33, 508, 2, 0, 0, "chunk4.4", "chunk4.16"),   # stride 256, L >= 64: LW 4; 16-bit SW 4 (staged), fp32 SW 16
+    (9, 510, 1, 0, 1, "chunk4.4", "chunk4.4"),     # stride 256, output off alignment: LW 4, SW 4
 ]
 
 
 @pytest.mark.parametrize("dt", ["f16", "bf16", "f32"])
-@pytest.mark.parametrize("m,n,pad,poff,ooff", CASES)
+@pytest.mark.parametrize("m,n,pad,poff,ooff", [c[:5] for c in CASES])
 def test_chunk_kernel_forms_vs_oracle(coracle, gpu, dt, m, n, pad, poff, ooff):
     seed = 31 * m + n + pad + 7 * poff + 3 * ooff
     for ov in ({}, {"nb": 5, "n2": 3, "a2_kind": "normal"}):

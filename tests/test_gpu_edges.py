@@ -35,6 +35,8 @@ from _helpers import DT_CODE, check_guarded as _check, dev_bytes as _dev_bytes, 
 pytestmark = pytest.mark.gpu
 
 # name: (n, extra packed bytes per row, packed byte offset, output element offset, dtypes, kernel)
+# (the kernel, and the load / store form a chunk entry's name states, are what the host plan
+# csrc/nf4_dequant_plan.h chooses: tests/test_dequant_plan_cpu.py asserts it)
 FORMS = {
     "dense": (1000, 0, 0, 0, ("bf16", "f16"), "chunk"),              # n % 8 == 0, rows of exactly 4 L bytes
     "dword_whole": (504, 4, 0, 0, ("bf16", "f32"), "chunk"),         # padded rows: dword loads, 16-byte stores

@@ -3,7 +3,9 @@ build, e.g. the parent commit's; ``--new`` this tree's by default), interleaved 
 process: bursts of back-to-back calls on one stream (no sync inside a burst), the host clock
 around the burst; the order of the two alternates burst by burst.
 
-Two routes.  ``abi``: the C entries by ctypes, the same arguments every call (the floor).
+Three routes.  ``abi``: the C entries by ctypes, the same arguments every call (the floor).
+``dq``: the same for the dequant entries -- nf4_dequant_ref on a flat (flat1 kernel), a
+dense-chunk and a piece-kernel shape, nf4_dequant_ref_batched with 24 matrices, nf4_dequant_bnb.
 ``py``: the package's own ``nf4_linear`` / ``nf4_linear_grouped`` (the whole call: argument
 preparation, output allocation, the ctypes call); the library behind them is switched
 burst by burst through ``_lib._lib``, which both read on every call.
@@ -46,12 +48,19 @@ CASES = {  # name: (route, M, K, Ns)
     "py_nf4_linear_m1_4096x4096": ("py", 1, 4096, (4096,)),
     "py_nf4_linear_grouped_qkv_m1": ("py", 1, 4096, (4096, 1024, 1024)),
 }
+DQ_CASES = {  # name: (entry, m, n, matrices)
+    "dq_ref_4096x4096_flat1": ("ref", 4096, 4096, 1),
+    "dq_ref_4096x4080_dense": ("ref", 4096, 4080, 1),
+    "dq_ref_4096x4090_piece": ("ref", 4096, 4090, 1),
+    "dq_ref_batched_24x1024x1024": ("batched", 1024, 1024, 24),
+    "dq_bnb_4096x4096": ("bnb", 4096, 4096, 1),
+}
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--base", default=None, help="the library to compare against")
 ap.add_argument("--new", default=os.path.join(REPO, "nf4_triton_dequantization_amd", "_lib", "libnf4dq.so"))
 ap.add_argument("--out", default="launch_cost_ab.jsonl")
-ap.add_argument("--case", default="all", choices=["all", *CASES])
+ap.add_argument("--case", default="all", choices=["all", "gemm", "dq", *CASES, *DQ_CASES])
 ap.add_argument("--calls", type=int, default=1000, help="calls per burst")
 ap.add_argument("--bursts", type=int, default=20, help="timed bursts per library (one more, untimed, first)")
 ap.add_argument("--only", default=None, choices=["new"], help="run this tree's library alone (kernel traces)")
@@ -99,9 +108,42 @@ def module(w, N, K):
                            in_features=K)
 
 
-def case(name, out):
+def dq_case(name):
+    """(record head, burst(L, calls) -> (t0, t1, the outputs to compare)) of a dequant case."""
+    entry, m, n, count = DQ_CASES[name]
+    stride, bpr = (n + 1) // 2, (n + 63) // 64
+    nb, n2 = m * bpr, m * ((bpr + 3) // 4)
+    ps = [torch.randint(0, 256, (m * stride,), dtype=torch.uint8, generator=g).to(dev) for _ in range(count)]
+    a1 = torch.randint(1, 256, (nb,), dtype=torch.uint8, generator=g).to(dev)
+    a2 = (torch.rand(n2, generator=g) * 0.1 + 0.01).to(dev)
+    code2 = torch.sort(torch.rand(256, generator=g) * 2 - 1).values.to(dev)
+    outs = [torch.empty(m, n, dtype=torch.bfloat16, device=dev) for _ in range(count)]
+    descs = (_lib.MatrixDesc * count)(*[_lib.MatrixDesc(p.data_ptr(), p.numel(), a1.data_ptr(), nb, a2.data_ptr(), n2,
+                                                        o.data_ptr(), m, n) for p, o in zip(ps, outs)])
+    st = torch.cuda.current_stream().cuda_stream
+
+    def burst(L, calls):
+        if entry == "ref":
+            f, a = L.nf4_dequant_ref, (ps[0].data_ptr(), ps[0].numel(), a1.data_ptr(), nb, a2.data_ptr(), n2,
+                                       outs[0].data_ptr(), _lib.BF16, m, n, st)
+        elif entry == "batched":
+            f, a = L.nf4_dequant_ref_batched, (descs, count, _lib.BF16, st)
+        else:
+            f, a = L.nf4_dequant_bnb, (ps[0].data_ptr(), a1.data_ptr(), nb, code2.data_ptr(), a2.data_ptr(), n2, 0.0,
+                                       outs[0].data_ptr(), _lib.BF16, m * n, 64, 256, st)
+        rcs = 0
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            rcs |= f(*a)
+        t1 = time.perf_counter()
+        assert rcs == 0, rcs
+        return t0, t1, outs
+
+    return {"case": name, "route": "dq", "entry": entry, "m": m, "n": n, "matrices": count}, burst
+
+
+def gemm_case(name):
     route, M, K, Ns = CASES[name]
-    calls, reps = ARGS.calls, ARGS.bursts
     ws_t = [weight(N, K) for N in Ns]
     x = torch.randn(M, K, generator=g).to(torch.bfloat16).to(dev)
     ys = [torch.empty(M, N, dtype=torch.bfloat16, device=dev) for N in Ns]
@@ -110,50 +152,60 @@ def case(name, out):
                                       for w, y, N in zip(ws_t, ys, Ns)])
     mods = [module(w, N, K) for w, N in zip(ws_t, Ns)]
     st = torch.cuda.current_stream().cuda_stream
+
+    def burst(L, calls):
+        if len(Ns) == 1:
+            wsz = L.nf4_gemm_workspace_bytes(M, Ns[0], K)
+        else:
+            wsz = L.nf4_gemm_grouped_workspace_bytes(M, K, mats, len(Ns), None)
+        ws = torch.zeros(max(wsz, 16), dtype=torch.uint8, device=dev)
+        w0 = ws_t[0]
+        _lib._lib = L  # the py route reads it on every call
+        last = None
+        torch.cuda.synchronize()
+        rcs = 0
+        t0 = time.perf_counter()
+        if route == "py" and len(Ns) == 1:
+            for _ in range(calls):
+                last = P.nf4_linear(x, mods[0])
+        elif route == "py":
+            for _ in range(calls):
+                last = P.nf4_linear_grouped(x, mods)
+        elif len(Ns) == 1:
+            f = L.nf4_gemm_ref
+            a = (x.data_ptr(), M, w0[0].data_ptr(), w0[0].numel(), w0[1].data_ptr(), w0[1].numel(),
+                 w0[2].data_ptr(), w0[2].numel(), ys[0].data_ptr(), _lib.BF16, Ns[0], K, ws.data_ptr(), wsz, st)
+            for _ in range(calls):
+                rcs |= f(*a)
+        else:
+            f = L.nf4_gemm_ref_grouped
+            a = (x.data_ptr(), M, K, mats, len(Ns), _lib.BF16, ws.data_ptr(), wsz, None, st)
+            for _ in range(calls):
+                rcs |= f(*a)
+        t1 = time.perf_counter()
+        assert rcs == 0, rcs
+        return t0, t1, ys if route == "abi" else (last if isinstance(last, list) else [last])
+
+    return {"case": name, "route": route, "M": M, "K": K, "Ns": list(Ns),
+            "wraps": any(wraps(N, K, w[1].numel(), w[2].numel()) for w, N in zip(ws_t, Ns))}, burst
+
+
+def case(name, out):
+    calls, reps = ARGS.calls, ARGS.bursts
+    rec, burst = dq_case(name) if name in DQ_CASES else gemm_case(name)
+    rec.update(calls_per_burst=calls, bursts=reps)
     times = {k: [] for k in LIBS}
     outs = {}
     for rep in range(reps + 1):
         order = list(LIBS) if rep % 2 == 0 else list(LIBS)[::-1]
         for k in order:
-            L = LIBS[k]
-            if len(Ns) == 1:
-                wsz = L.nf4_gemm_workspace_bytes(M, Ns[0], K)
-            else:
-                wsz = L.nf4_gemm_grouped_workspace_bytes(M, K, mats, len(Ns), None)
-            ws = torch.zeros(max(wsz, 16), dtype=torch.uint8, device=dev)
-            w0 = ws_t[0]
-            _lib._lib = L  # the py route reads it on every call
-            last = None
             torch.cuda.synchronize()
-            rcs = 0
-            t0 = time.perf_counter()
-            if route == "py" and len(Ns) == 1:
-                for _ in range(calls):
-                    last = P.nf4_linear(x, mods[0])
-            elif route == "py":
-                for _ in range(calls):
-                    last = P.nf4_linear_grouped(x, mods)
-            elif len(Ns) == 1:
-                f = L.nf4_gemm_ref
-                a = (x.data_ptr(), M, w0[0].data_ptr(), w0[0].numel(), w0[1].data_ptr(), w0[1].numel(),
-                     w0[2].data_ptr(), w0[2].numel(), ys[0].data_ptr(), _lib.BF16, Ns[0], K, ws.data_ptr(), wsz, st)
-                for _ in range(calls):
-                    rcs |= f(*a)
-            else:
-                f = L.nf4_gemm_ref_grouped
-                a = (x.data_ptr(), M, K, mats, len(Ns), _lib.BF16, ws.data_ptr(), wsz, None, st)
-                for _ in range(calls):
-                    rcs |= f(*a)
-            t1 = time.perf_counter()
+            t0, t1, res = burst(LIBS[k], calls)
             torch.cuda.synchronize()
             t2 = time.perf_counter()
-            assert rcs == 0, rcs
-            res = ys if route == "abi" else (last if isinstance(last, list) else [last])
             outs.setdefault(k, [y.clone() for y in res])
             if rep:  # the first round warms up
                 times[k].append({"host_us": (t1 - t0) / calls * 1e6, "drained_us": (t2 - t0) / calls * 1e6})
-    rec = {"case": name, "route": route, "M": M, "K": K, "Ns": list(Ns), "calls_per_burst": calls, "bursts": reps,
-           "wraps": any(wraps(N, K, w[1].numel(), w[2].numel()) for w, N in zip(ws_t, Ns))}
     if "parent" in outs:
         rec["outputs_bit_identical"] = all(torch.equal(a.view(torch.int16), b.view(torch.int16))
                                            for a, b in zip(outs["parent"], outs["new"]))
@@ -166,11 +218,13 @@ def case(name, out):
     if "parent" in rec:
         p = rec["parent"]
         rec["new_median_within_parent_spread"] = p["host_us_min"] <= rec["new"]["host_us_median"] <= p["host_us_max"]
+        rec["new_median_within_or_below_parent_spread"] = rec["new"]["host_us_median"] <= p["host_us_max"]
     print(json.dumps(rec), flush=True)
     out.write(json.dumps(rec) + "\n")
     out.flush()
 
 
 with open(ARGS.out, "w") as out:
-    for name in (CASES if ARGS.case == "all" else [ARGS.case]):
+    groups = {"all": [*CASES, *DQ_CASES], "gemm": list(CASES), "dq": list(DQ_CASES)}
+    for name in groups.get(ARGS.case, [ARGS.case]):
         case(name, out)
