@@ -330,6 +330,51 @@ int nf4_gemm_bnb_single(const void* x, int64_t M, const uint8_t* packed, int64_t
                         void* y, int32_t out_dtype, int64_t N, int64_t K,
                         void* workspace, size_t workspace_bytes, const nf4_gemm_cfg* cfg, void* hip_stream);
 
+/* Several weights in bitsandbytes semantics that share the activation x (q/k/v, gate/up):
+ * one launch.  `mats` points at `count` nf4_gemm_bnb_mat (it is `const void*` so that every
+ * prototype of this header keeps to the plain parameter types bindings are derived from).
+ * Every weight has its own code2 table, offset pointer, blocksize and blocksize2, and its
+ * statistics are indexed on its own flat stream (64-block f = row_in_weight * (K / 64) +
+ * block, from 0 for each weight); the values are nf4_gemm_bnb's / nf4_gemm_bnb_single's per
+ * weight, bit for bit in the weights entering the products.  All weights of a call are
+ * nested (single == 0) or all have fp32 statistics (single != 0: absmax_q, code2, offset
+ * and blocksize2 are ignored; absmax2 / n2 are the fp32 absmax and its length).
+ * Rules: nf4_gemm_bnb's per weight (block sizes, null fields: NF4DQ_ERR_ARG; N % 64,
+ * packed_len, statistics lengths: NF4DQ_ERR_SHAPE) and nf4_gemm_ref_grouped's for the group
+ * (count <= NF4DQ_GEMM_GROUP_MAX, K % 128 == 0, M <= NF4DQ_GEMM_MAX_M; an N == 0 weight is
+ * accepted by the families that number column groups per weight -- K128 and XR -- and is
+ * NF4DQ_ERR_SHAPE under the persistent kernel).  count == 0, M == 0 or no columns at all:
+ * NF4DQ_OK, nothing launched.
+ * cfg NULL = the library's choice: one launch -- what nf4_gemm_ref_grouped runs for the
+ * column total where that family has the grouped mode and every blocksize is 64, the
+ * persistent kernel where that would be the decode GEMV, else the 128-deep kernel; only a
+ * persistent choice that cannot run falls back to one nf4_gemm_bnb launch per weight.  A cfg
+ * may name NF4DQ_GEMM_K128, _PERSIST or _XR; any other family, or any but K128 when a weight
+ * has blocksize > 64, is NF4DQ_ERR_ARG, and a named cfg never falls back.  The decode GEMV,
+ * the streaming and the shared-activation kernels do not have the grouped mode.  A call with
+ * one weight runs as nf4_gemm_bnb / nf4_gemm_bnb_single does.
+ * Workspace (nf4_gemm_bnb_grouped_workspace_bytes), its zero-fill contract, the split-K
+ * error word and nf4_gemm_check_workspace: exactly as for nf4_gemm_ref_grouped.
+ * Asynchronous on `hip_stream`; allocates nothing. */
+typedef struct nf4_gemm_bnb_mat {
+    const uint8_t* packed;
+    int64_t packed_len;      /* N*K/2 */
+    const uint8_t* absmax_q; /* nested; NULL in single mode */
+    int64_t nb;              /* nested; 0 in single mode */
+    const float* code2;      /* nested: 256 fp32 on the device; NULL in single mode */
+    const float* absmax2;    /* nested: absmax2; single: the fp32 absmax */
+    int64_t n2;              /* ... and its length */
+    const float* offset;     /* nested: ONE fp32 on the device, or NULL (= 0) */
+    int32_t blocksize, blocksize2; /* per weight; blocksize2 ignored in single mode */
+    void* y;
+    int64_t N;
+} nf4_gemm_bnb_mat;
+size_t nf4_gemm_bnb_grouped_workspace_bytes(int64_t M, int64_t K, const void* mats, int32_t count,
+                                            int32_t single, const nf4_gemm_cfg* cfg);
+int nf4_gemm_bnb_grouped(const void* x, int64_t M, int64_t K, const void* mats, int32_t count,
+                         int32_t single, int32_t out_dtype, void* workspace, size_t workspace_bytes,
+                         const nf4_gemm_cfg* cfg, void* hip_stream);
+
 /* The split-K hand-off never hangs: a reducer that has polled a partner slice's
  * entries 2^16 times without seeing them gives up, reads them as NaN and sets a
  * sticky error word in the workspace header.  This call waits for `hip_stream`,

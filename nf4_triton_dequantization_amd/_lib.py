@@ -87,6 +87,15 @@ class GemmMat(ctypes.Structure):
                 ("y", ctypes.c_void_p), ("N", ctypes.c_int64)]
 
 
+class GemmBnbMat(ctypes.Structure):
+    """nf4_gemm_bnb_mat (include/nf4_dequant.h): one weight of nf4_gemm_bnb_grouped."""
+
+    _fields_ = [("packed", ctypes.c_void_p), ("packed_len", ctypes.c_int64), ("absmax_q", ctypes.c_void_p),
+                ("nb", ctypes.c_int64), ("code2", ctypes.c_void_p), ("absmax2", ctypes.c_void_p),
+                ("n2", ctypes.c_int64), ("offset", ctypes.c_void_p), ("blocksize", ctypes.c_int32),
+                ("blocksize2", ctypes.c_int32), ("y", ctypes.c_void_p), ("N", ctypes.c_int64)]
+
+
 class GemmCfg(ctypes.Structure):
     """nf4_gemm_cfg (include/nf4_dequant.h)."""
 
@@ -126,6 +135,10 @@ SIGNATURES = {
                                     _P, ctypes.c_size_t, ctypes.POINTER(GemmCfg), _P]),
     "nf4_gemm_bnb_single": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _I32, _P, _I32, _I64, _I64, _P,
                                            ctypes.c_size_t, ctypes.POINTER(GemmCfg), _P]),
+    # `mats`: const void* in the header, pointing at GemmBnbMat[count]
+    "nf4_gemm_bnb_grouped_workspace_bytes": (ctypes.c_size_t, [_I64, _I64, _P, _I32, _I32, ctypes.POINTER(GemmCfg)]),
+    "nf4_gemm_bnb_grouped": (ctypes.c_int, [_P, _I64, _I64, _P, _I32, _I32, _I32, _P, ctypes.c_size_t,
+                                            ctypes.POINTER(GemmCfg), _P]),
     "nf4_gemm_check_workspace": (ctypes.c_int, [_P, ctypes.c_size_t, _P]),
     "nf4_strerror": (ctypes.c_char_p, [ctypes.c_int]),
     "nf4_version": (ctypes.c_char_p, []),

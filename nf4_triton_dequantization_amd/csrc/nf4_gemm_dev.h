@@ -29,6 +29,13 @@
 //    walking strip groups (M <= 16), the ring running on across groups.
 // (The seventh, the decode GEMV for M = 1 -- no MFMA, the exact weights dotted with x on
 // the VALU -- lives with its launcher in nf4_gemm_launch_gemv.hip.)
+// Scale modes (SM): the reference repository's, and the two bitsandbytes ones (block_scale).
+// The persistent, register-resident and 128-deep kernels also have the GROUPED form of the
+// bitsandbytes modes (template flag GRP, nf4_gemm_bnb_grouped): several weights in one launch,
+// each with its own code2 table, offset pointer and block sizes, read from a side table behind
+// the argument struct (GemmArgsG / StreamArgsG; the structs of every other launch keep their
+// sizes), its statistics indexed on its own flat stream.  The decode GEMV, the streaming and
+// the shared-activation kernel do not have the grouped mode.
 // All use the same k permutation on A and B fragments (a lane's packed dword
 // is exactly its MFMA B fragment of one step), so no shuffle is needed.  K
 // slices over workgroups (ksplit > 1) write fp32 partials to a workspace slab;
@@ -42,6 +49,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "../../include/nf4_dequant.h"
 #include "nf4_common.h"
@@ -346,6 +355,35 @@ struct GemmArgs {
     uint32_t sh, sh2;       // log2(blocksize / 64), log2(blocksize2)
 };
 
+// Grouped bitsandbytes launches (nf4_gemm_bnb_grouped; the kernels' template flag GRP): each
+// weight has its own code2 table, offset and block sizes, in a side table behind the
+// argument struct of the family.  The structs of the existing launches keep their sizes
+// (24 more bytes in StreamArgs cost the reference-mode persistent launches 2-4 %,
+// profiles/gemm_bnb/): the grouped-bnb instantiations alone take the longer struct.
+struct BnbSide {
+    const float* code2;     // [256] (nested)
+    const float* offset;    // [1] or null (= 0)
+    uint32_t sh, sh2;       // log2(blocksize / 64), log2(blocksize2)
+};
+struct GemmArgsG : GemmArgs {
+    BnbSide side[kK128GroupMax];  // side[i] belongs to mat[i]
+};
+template <bool GRP>
+using GemmArgsOf = typename std::conditional<GRP, GemmArgsG, GemmArgs>::type;
+static_assert(sizeof(K128Mat) == 72 && sizeof(GemmArgs) == 672, "the existing launches' kernel arguments keep their size");
+
+// The code2 table and the offset of weight mi: the launch-wide ones, or (GRP) its own.
+template <bool GRP>
+__device__ __forceinline__ const float* side_code2(const GemmArgsOf<GRP>& A, uint32_t mi) {
+    if constexpr (GRP) return A.side[mi].code2;
+    else return A.code2;
+}
+template <bool GRP>
+__device__ __forceinline__ const float* side_offset(const GemmArgsOf<GRP>& A, uint32_t mi) {
+    if constexpr (GRP) return A.side[mi].offset;
+    else return A.offset;
+}
+
 // The scale modes (nf4_gemm_plan.h).  In the bnb modes a 64-block is numbered on the flat
 // stream, f = row * bpr + block of the row, its statistics block is i = f >> sh, and
 //   nested:  s = fl32(fl32(code2[a1[i]] * a2[i >> sh2]) + offset)   (two roundings; the
@@ -389,10 +427,10 @@ struct Chunk {
 };
 
 // VS: the block scales come from the workgroup's LDS table (nf4_gemm_smallm_kernel), no per-chunk gathers
-template <int MT, int NT, bool VS, int SM>
-__device__ __forceinline__ void chunk_issue(const GemmArgs& A, const K128Mat& Mt, __amdgpu_buffer_rsrc_t rw,
+template <int MT, int NT, bool VS, int SM, bool GRP = false>
+__device__ __forceinline__ void chunk_issue(const GemmArgsOf<GRP>& A, const K128Mat& Mt, __amdgpu_buffer_rsrc_t rw,
                                             __amdgpu_buffer_rsrc_t rx, uint32_t c, bool valid, uint32_t row,
-                                            uint32_t nl, uint32_t kh, Chunk<MT, NT>& in) {
+                                            uint32_t nl, uint32_t kh, uint32_t mi, Chunk<MT, NT>& in) {
     const uint32_t kbase = c * kChunkK + 32u * kh;
     // past the wave's last chunk: offsets beyond the buffer ranges (zeros, no traffic)
 #pragma unroll
@@ -414,9 +452,15 @@ __device__ __forceinline__ void chunk_issue(const GemmArgs& A, const K128Mat& Mt
                 in.qa[nt] = Mt.a1[fmodu(r * A.bpr + b, Mt.nb)];             // (:173-177 wrap)
                 in.qb[nt] = Mt.a2[fmodu(r * A.groups + (b >> 2), Mt.n2)];  // (:40-41, :183-186 wrap)
             } else {
-                const uint32_t i = (r * A.bpr + b) >> A.sh;  // statistics block on the flat stream
-                if constexpr (SM == kScaleBnb) in.qa[nt] = Mt.a1[i];
-                in.qb[nt] = Mt.a2[SM == kScaleBnb ? i >> A.sh2 : i];
+                if constexpr (GRP) {  // the weight's own block sizes, its own flat stream
+                    const uint32_t i = (r * A.bpr + b) >> A.side[mi].sh;
+                    if constexpr (SM == kScaleBnb) in.qa[nt] = Mt.a1[i];
+                    in.qb[nt] = Mt.a2[SM == kScaleBnb ? i >> A.side[mi].sh2 : i];
+                } else {
+                    const uint32_t i = (r * A.bpr + b) >> A.sh;  // statistics block on the flat stream
+                    if constexpr (SM == kScaleBnb) in.qa[nt] = Mt.a1[i];
+                    in.qb[nt] = Mt.a2[SM == kScaleBnb ? i >> A.sh2 : i];
+                }
             }
         }
     }
@@ -460,13 +504,19 @@ __device__ __forceinline__ void chunk_mma(const Chunk<MT, NT>& in, const float* 
 // Workgroup = WV waves owning 16 NT output columns (NT strips) of one K slice;
 // wave w takes every WV-th group of D chunks, D chunks in flight at a time; the
 // waves' partial sums are combined through LDS (fixed order, one strip at a time).
-template <int DT, int MT, int D, int WV, int NT, bool VS, int SM = kScaleRef>
-__global__ __launch_bounds__(64 * WV) void nf4_gemm_smallm_kernel(const GemmArgs A) {
+// GRP (grouped bitsandbytes launch): a workgroup owns one column group of one weight, so its
+// code2 table, offset and block sizes are that weight's (side[mi]), and its statistics are
+// indexed on that weight's own flat stream (rows count from the weight's first).
+template <int DT, int MT, int D, int WV, int NT, bool VS, int SM = kScaleRef, bool GRP = false>
+__global__ __launch_bounds__(64 * WV) void nf4_gemm_smallm_kernel(const GemmArgsOf<GRP> A) {
     constexpr int kGemmWaves = WV;
     __shared__ __attribute__((aligned(16))) float lut[20];  // 16 codes + the last-arriver flag
     __shared__ float c2tab[SM == kScaleBnb && !VS ? 256 : 1];  // nested mode, gathered scales: code2
-    const float c2v = VS ? 0.0f : load_code2<SM>(A.code2);
-    const float off = load_offset<SM>(A.offset);
+    uint32_t mi_side = 0;  // GRP: the workgroup's weight, found before the table loads
+    if constexpr (GRP)
+        for (uint32_t i = 1; i < A.nmat; ++i) mi_side = blockIdx.x % A.col_groups >= A.mat[i].cg_begin ? i : mi_side;
+    const float c2v = VS ? 0.0f : load_code2<SM>(side_code2<GRP>(A, mi_side));
+    const float off = load_offset<SM>(side_offset<GRP>(A, mi_side));
     __shared__ __attribute__((aligned(16))) f32x4 red[WV][MT][64];
     extern __shared__ __attribute__((aligned(16))) float scl[];  // VS: [16 NT rows][2 chunks_per_split blocks]
     const uint32_t lane = threadIdx.x & 63u;
@@ -499,7 +549,7 @@ __global__ __launch_bounds__(64 * WV) void nf4_gemm_smallm_kernel(const GemmArgs
     for (uint32_t g = c0 + wave * D; g < c1 || first; g += kGemmWaves * D) {
         Chunk<MT, NT> ch[D];
 #pragma unroll
-        for (int d = 0; d < D; ++d) chunk_issue<MT, NT, VS, SM>(A, Mt, rw, rx, g + d, g + d < c1, row, nl, kh, ch[d]);
+        for (int d = 0; d < D; ++d) chunk_issue<MT, NT, VS, SM, GRP>(A, Mt, rw, rx, g + d, g + d < c1, row, nl, kh, mi, ch[d]);
         if (first) {  // LUT (+ VS: the slice's scale table) and the barrier overlap the first loads
             write_lut(lut);
             if constexpr (SM == kScaleBnb && !VS)
@@ -518,9 +568,16 @@ __global__ __launch_bounds__(64 * WV) void nf4_gemm_smallm_kernel(const GemmArgs
                             scl[i] = (q / 127.0f) * Mt.a2[fmodu(r * A.groups, Mt.n2) + (gb >> 2)];
                         } else {
                             // once per block and launch: code2 straight from memory (block_scale)
-                            const uint32_t sb = (r * A.bpr + gb) >> A.sh;
-                            if constexpr (SM == kScaleBnb) scl[i] = A.code2[Mt.a1[sb]] * Mt.a2[sb >> A.sh2] + off;
-                            else scl[i] = Mt.a2[sb];
+                            if constexpr (GRP) {
+                                const BnbSide& sd = A.side[mi];
+                                const uint32_t sb = (r * A.bpr + gb) >> sd.sh;
+                                if constexpr (SM == kScaleBnb) scl[i] = sd.code2[Mt.a1[sb]] * Mt.a2[sb >> sd.sh2] + off;
+                                else scl[i] = Mt.a2[sb];
+                            } else {
+                                const uint32_t sb = (r * A.bpr + gb) >> A.sh;
+                                if constexpr (SM == kScaleBnb) scl[i] = A.code2[Mt.a1[sb]] * Mt.a2[sb >> A.sh2] + off;
+                                else scl[i] = Mt.a2[sb];
+                            }
                         }
                     }
                 }
@@ -782,6 +839,12 @@ struct XSlot {
     uint8_t qa[NSC];  // kept 8-bit: a widening right after the load would wait for it (a drained ring)
     float qb[NSC];
 };
+template <int KPW>
+struct XSlotG : XSlot<KPW> {
+    uint32_t mi;  // grouped bnb modes: the strip's weight (uniform), for its table at consume time
+};
+template <int KPW, bool GRP>
+using XSlotOf = typename std::conditional<GRP, XSlotG<KPW>, XSlot<KPW>>::type;
 
 // The weight owning a strip: straight-line selects over the group (no loop in
 // the strip loop -- a loop there costs the ring its counted waits)
@@ -811,9 +874,19 @@ struct XMat {
     FastDiv nb, n2;
     uint32_t begin, next;  // [begin, next): the cached weight's strips in the launch
 };
+struct XMatG : XMat {
+    uint32_t mi, sh2;  // grouped bnb modes: the weight and its log2(blocksize2)
+};
+template <bool GRP>
+using XMatOf = typename std::conditional<GRP, XMatG, XMat>::type;
 
-__device__ __forceinline__ void xmat_load(const GemmArgs& A, uint32_t strip, XMat& m) {
+template <bool GRP>
+__device__ __forceinline__ void xmat_load(const GemmArgsOf<GRP>& A, uint32_t strip, XMatOf<GRP>& m) {
     const uint32_t mi = xr_mat_of(A, strip);
+    if constexpr (GRP) {
+        m.mi = mi;
+        m.sh2 = A.side[mi].sh2;
+    }
     const K128Mat& Mt = A.mat[mi];
     m.rw = __builtin_amdgcn_make_buffer_rsrc((void*)Mt.packed, 0, Mt.N * (A.K >> 1), kRsrcFlags);
     m.ra1 = __builtin_amdgcn_make_buffer_rsrc((void*)Mt.a1, 0, Mt.nb.d, kRsrcFlags);
@@ -824,10 +897,11 @@ __device__ __forceinline__ void xmat_load(const GemmArgs& A, uint32_t strip, XMa
     m.next = mi + 1u < A.nmat ? A.mat[mi + 1u].cg_begin : 0xFFFFFFFFu;
 }
 
-template <int KPW, int SM>
-__device__ __forceinline__ void xslot_issue(const GemmArgs& A, uint32_t strip, bool valid, uint32_t cw,
-                                            const XLane& ln, XMat& Mt, XSlot<KPW>& s) {
-    if (strip >= Mt.next) xmat_load(A, strip, Mt);  // uniform; scalar loads only
+template <int KPW, int SM, bool GRP>
+__device__ __forceinline__ void xslot_issue(const GemmArgsOf<GRP>& A, uint32_t strip, bool valid, uint32_t cw,
+                                            const XLane& ln, XMatOf<GRP>& Mt, XSlotOf<KPW, GRP>& s) {
+    if (strip >= Mt.next) xmat_load<GRP>(A, strip, Mt);  // uniform; scalar loads only
+    if constexpr (GRP) s.mi = Mt.mi;
     const uint32_t r0 = (strip - Mt.begin) * 16u;  // first row of the strip (uniform)
     const __amdgpu_buffer_rsrc_t rw = Mt.rw, ra1 = Mt.ra1, ra2 = Mt.ra2;
     constexpr int NSC = XSlot<KPW>::NSC;
@@ -851,7 +925,12 @@ __device__ __forceinline__ void xslot_issue(const GemmArgs& A, uint32_t strip, b
         } else {
             const uint32_t f = r0 * A.bpr + 2u * c + ln.b1;  // the lane's 64-block on the flat stream (sh = 0)
             if constexpr (SM == kScaleBnb) s.qa[h] = (uint8_t)NF4_ABL_SLOAD(ra1, f | oob, true);
-            s.qb[h] = __uint_as_float(NF4_ABL_SLOAD(ra2, ((SM == kScaleBnb ? f >> A.sh2 : f) * 4u) | oob, false));
+            uint32_t i2 = f;
+            if constexpr (SM == kScaleBnb) {
+                if constexpr (GRP) i2 = f >> Mt.sh2;
+                else i2 = f >> A.sh2;
+            }
+            s.qb[h] = __uint_as_float(NF4_ABL_SLOAD(ra2, (i2 * 4u) | oob, false));
         }
     }
 }
@@ -927,8 +1006,12 @@ __device__ __forceinline__ void xr_pair_mma(const u32x4& w0, const u32x4& w1, fl
 // 4-11 of the next) the 16 lanes then hit 16 distinct 4-bank sets.
 __device__ __forceinline__ uint32_t xr_xsw(uint32_t r) { return r ^ ((((r + 4u) >> 3) & 1u) << 3); }
 
-template <int DT, int MT, int WV, int KPW, int D, int GU, int SM>
-__device__ __forceinline__ void xr_body(const GemmArgs& A) {
+// GRP (grouped bitsandbytes launch, nested): a workgroup's strips cross weight boundaries at
+// any strip, so every weight's code2 table (nmat x 1 KiB) and offset sit in LDS behind the
+// held results (the plan's xr_lds_dynamic counts them); a ring slot carries its weight's
+// index from issue to consumption, where the strip's table and offset are picked by it.
+template <int DT, int MT, int WV, int KPW, int D, int GU, int SM, bool GRP>
+__device__ __forceinline__ void xr_body(const GemmArgsOf<GRP>& A) {
     extern __shared__ __attribute__((aligned(16))) f32x4 xr_smem[];  // dynamic part (host: xr_lds_dynamic)
     // 256-deep chunks: the pair table (64 KiB) and the q/127 table, static so that the
     // lookups' addresses need no base added (one VALU per two weights less than in a
@@ -936,8 +1019,21 @@ __device__ __forceinline__ void xr_body(const GemmArgs& A) {
     __shared__ __attribute__((aligned(16))) f32x2 xr_ptab[KPW >= 2 ? 256 * 32 : 2];
     __shared__ float xr_qtab[KPW >= 2 || SM == kScaleBnb ? 256 : 4];  // q / 127, or code2 (nested mode)
     static_assert(sizeof(xr_ptab) + sizeof(xr_qtab) <= xr_lds_static(KPW, SM), "the plan's static LDS covers the tables");
-    const float c2v = load_code2<SM>(A.code2);
-    const float off = load_offset<SM>(A.offset);
+    constexpr bool kTabs = GRP && SM == kScaleBnb;  // per-weight tables in the dynamic region
+    constexpr int kOneTab = kTabs ? kScaleRef : SM;  // with per-weight tables no launch-wide table or offset
+    const float c2v = load_code2<kOneTab>(A.code2);
+    const float off = load_offset<kOneTab>(A.offset);
+    // entries e = threadIdx.x + i 64 WV of the nmat x 256 tables: a wave's 64 are one weight's
+    constexpr int kTabRegs = kTabs ? kK128GroupMax * 256 / (64 * WV) : 1;
+    float c2g[kTabRegs];
+    if constexpr (kTabs) {
+#pragma unroll
+        for (int i = 0; i < kTabRegs; ++i) {
+            const uint32_t e = threadIdx.x + (uint32_t)i * 64u * WV;
+            const uint32_t wi = __builtin_amdgcn_readfirstlane(e >> 8);
+            c2g[i] = wi < A.nmat ? A.side[wi].code2[e & 255u] : 0.0f;
+        }
+    }
     f32x2* ptab = xr_ptab;
     float* qtab = xr_qtab;
     // partial tiles meet once per R strips (8 waves: two strips per barrier)
@@ -947,6 +1043,8 @@ __device__ __forceinline__ void xr_body(const GemmArgs& A) {
     float* lut = reinterpret_cast<float*>(red + 2 * R * WV * MT * 64);  // 16 codes
     uint32_t* last_flags = reinterpret_cast<uint32_t*>(lut + 16);        // [64] split-K tickets drawn last
     float* held = reinterpret_cast<float*>(last_flags + 64);            // [T][16 MT][16] fp32 results
+    float* gtab = held + A.per_wg * (16u * MT * 16u);                    // kTabs: [nmat][256] code2, then
+    float* goff = gtab + A.nmat * 256u;                                  //        [nmat] offsets
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t nl = lane & 15u, kh = lane >> 4;
@@ -1012,12 +1110,12 @@ __device__ __forceinline__ void xr_body(const GemmArgs& A) {
     }
     __builtin_amdgcn_sched_barrier(0);  // issue order = wait order: x, then the ring slot by slot
     NF4_GSTAMP(11);
-    XSlot<KPW> ring[D];
-    XMat xm;
-    xmat_load(A, s0, xm);
+    XSlotOf<KPW, GRP> ring[D];
+    XMatOf<GRP> xm;
+    xmat_load<GRP>(A, s0, xm);
 #pragma unroll
     for (int d = 0; d < D; ++d) {
-        xslot_issue<KPW, SM>(A, s0 + (uint32_t)d, (uint32_t)d < nst, cw, ln, xm, ring[d]);
+        xslot_issue<KPW, SM, GRP>(A, s0 + (uint32_t)d, (uint32_t)d < nst, cw, ln, xm, ring[d]);
         __builtin_amdgcn_sched_barrier(0);
     }
     NF4_GSTAMP(10);
@@ -1043,8 +1141,19 @@ __device__ __forceinline__ void xr_body(const GemmArgs& A) {
         __syncthreads();  // every wave's fragments out of the pair table's region before the tables
     }
     write_lut(lut);
-    if constexpr (SM == kScaleBnb)
+    if constexpr (kTabs) {
+#pragma unroll
+        for (int i = 0; i < kTabRegs; ++i) {
+            const uint32_t e = tid + (uint32_t)i * 64u * WV;
+            if (e < A.nmat * 256u) gtab[e] = c2g[i];
+        }
+        for (uint32_t i = 0; i < A.nmat; ++i) {  // uniform: one scalar load each
+            const float o = load_offset<SM>(A.side[i].offset);
+            if (tid == 0) goff[i] = o;
+        }
+    } else if constexpr (SM == kScaleBnb) {
         if (tid < 256u) qtab[tid] = c2v;
+    }
     if constexpr (KPW >= 2) {  // tables while the loads fly (as the streaming kernels)
         if constexpr (SM == kScaleRef)
             if (tid < 256u) qtab[tid] = (float)tid / 127.0f;  // IEEE division (:45)
@@ -1075,6 +1184,11 @@ __device__ __forceinline__ void xr_body(const GemmArgs& A) {
     for (int gi = 0; gi < (GU > 0 ? GU : 1); ++gi)
 #pragma unroll
         for (int q = 0; q < 4; ++q) gotg[gi][q] = 0;
+    // a strip's block scale: its weight's table and offset where the launch keeps one per weight
+    auto strip_scale = [&](const XSlotOf<KPW, GRP>& sl, int h) __attribute__((always_inline)) {
+        if constexpr (kTabs) return block_scale<SM>(gtab + 256u * sl.mi, sl.qa[h], sl.qb[h], goff[sl.mi]);
+        else return block_scale<SM>(qtab, sl.qa[h], sl.qb[h], off);
+    };
     auto group = [&](uint32_t t0, uint64_t (&gg)[4]) __attribute__((always_inline)) {
         f32x4 accs[R][MT];  // the partials of the current reduction group (R strips)
 #pragma unroll
@@ -1090,7 +1204,7 @@ __device__ __forceinline__ void xr_body(const GemmArgs& A) {
                     for (int h = 0; h < KPW / 2; ++h) {
                         const u32x4 (&xs)[2][MT][4] = *reinterpret_cast<const u32x4 (*)[2][MT][4]>(&xf[2 * h]);
                         xr_pair_mma<DT, MT>(ring[d].w[2 * h], ring[d].w[2 * h + 1],
-                                            block_scale<SM>(qtab, ring[d].qa[h], ring[d].qb[h], off), ptab, slot8,
+                                            strip_scale(ring[d], h), ptab, slot8,
                                             xs, acc);
                     }
                 }
@@ -1105,6 +1219,7 @@ __device__ __forceinline__ void xr_body(const GemmArgs& A) {
                         for (int s = 0; s < 4; ++s) ch.x[mt][s] = xf[q][mt][s];
                     float sc1;
                     if constexpr (SM == kScaleRef) sc1 = ((float)ring[d].qa[q / 2] / 127.0f) * ring[d].qb[q / 2];  // IEEE division (:45)
+                    else if constexpr (kTabs) sc1 = strip_scale(ring[d], q / 2);
                     else sc1 = block_scale<SM>(qtab, ring[d].qa[q / 2], ring[d].qb[q / 2], off);
                     const float scs[1] = {sc1};
                     f32x4 a1[MT][1];
@@ -1116,7 +1231,7 @@ __device__ __forceinline__ void xr_body(const GemmArgs& A) {
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-            xslot_issue<KPW, SM>(A, s0 + t + (uint32_t)D, t + (uint32_t)D < nst, cw, ln, xm, ring[d]);
+            xslot_issue<KPW, SM, GRP>(A, s0 + t + (uint32_t)D, t + (uint32_t)D < nst, cw, ln, xm, ring[d]);
             __builtin_amdgcn_sched_barrier(0);
             if (d % R != R - 1) continue;  // the group's partials meet after its last strip
             const uint32_t tg = t + 1u - (uint32_t)R;  // first strip of the group
@@ -1316,18 +1431,18 @@ __device__ __forceinline__ void xr_body(const GemmArgs& A) {
     NF4_GSTAMP(9);
 }
 
-template <int DT, int MT, int WV, int KPW, int D, int GU, int SM = kScaleRef>
-__global__ __launch_bounds__(64 * WV) void nf4_gemm_xr_kernel(const GemmArgs A) {
-    xr_body<DT, MT, WV, KPW, D, GU, SM>(A);
+template <int DT, int MT, int WV, int KPW, int D, int GU, int SM = kScaleRef, bool GRP = false>
+__global__ __launch_bounds__(64 * WV) void nf4_gemm_xr_kernel(const GemmArgsOf<GRP> A) {
+    xr_body<DT, MT, WV, KPW, D, GU, SM, GRP>(A);
 }
 // GU > 0: the unrolled groups keep 4 x 4 exchange results per lane live across the
 // loop; at one workgroup of 8 waves per CU (2 per SIMD) the kernel may use up to
 // 256 registers, and with the default budget the allocator moved those results
 // between registers (each move a full vmcnt(0) drain inside the ring)
-template <int DT, int MT, int WV, int KPW, int D, int GU, int SM = kScaleRef>
+template <int DT, int MT, int WV, int KPW, int D, int GU, int SM = kScaleRef, bool GRP = false>
 __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(1, 2))) void nf4_gemm_xrg_kernel(
-    const GemmArgs A) {
-    xr_body<DT, MT, WV, KPW, D, GU, SM>(A);
+    const GemmArgsOf<GRP> A) {
+    xr_body<DT, MT, WV, KPW, D, GU, SM, GRP>(A);
 }
 
 // ---------------------------------------------------------------------------
@@ -1395,6 +1510,15 @@ struct StreamArgs {
     uint32_t out_off;       // persistent: finished outputs [group][strip][M][16] (16-bit)
 };
 static_assert(sizeof(BnbFields) <= sizeof(StreamMat), "the bnb fields fit the second weight's slot");
+// Grouped bitsandbytes launches: the per-weight side table behind the struct (see GemmArgsG);
+// `bnb` above is not read then (it lies over mat[1]).
+struct StreamArgsG : StreamArgs {
+    BnbSide side[kGroupMax];  // side[i] belongs to mat[i]
+};
+template <bool GRP>
+using StreamArgsOf = typename std::conditional<GRP, StreamArgsG, StreamArgs>::type;
+static_assert(sizeof(StreamMat) == 80 && sizeof(StreamArgs) == 752,
+              "the existing launches' kernel arguments keep their size");
 
 struct SSlot {
     u32x4 w0, w1;
@@ -1754,16 +1878,37 @@ __device__ __forceinline__ typename PScales<P>::vec pload(__amdgpu_buffer_rsrc_t
 struct PGeo {  // where the ring issues: one strip of one weight
     __amdgpu_buffer_rsrc_t rw, ra1, ra2;
     uint32_t row, b1, b2;
+    uint32_t sh2;    // grouped nested mode: log2(blocksize2) of that weight
     uint32_t wbase;  // the lane's first weight byte of the slice: row K / 2 + kh 32 + chunk base 128
 };
 
-template <int DT, int W, int P, bool SPLIT, int SM = kScaleRef>
-__global__ __launch_bounds__(64 * W) void nf4_gemm_persist_kernel(const StreamArgs A) {
+// GRP (grouped bitsandbytes launch, nested): a workgroup's walk crosses weight boundaries, and
+// the issue pointer runs a round ahead of consumption.  So log2(blocksize2) travels with the
+// issue pointer (PGeo::sh2), while the code2 table and the offset are those of the weight
+// being CONSUMED (cmi): one 1 KiB table in LDS, reloaded when the next group to consume
+// belongs to another weight -- workgroup-uniform, between the group's reduction barrier (every
+// wave has made its last scale of the old weight) and a barrier of its own, at most
+// nmat - 1 times per workgroup.  The plan's LDS accounting is that of the reference mode.
+template <int DT, int W, int P, bool SPLIT, int SM = kScaleRef, bool GRP = false>
+__global__ __launch_bounds__(64 * W) void nf4_gemm_persist_kernel(const StreamArgsOf<GRP> A) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ __attribute__((aligned(16))) f32x2 ptab[256 * 32];
     __shared__ float qtab[256];  // q / 127, or code2 (nested mode)
-    const float c2v = load_code2<SM>(A.bnb.f.code2);
-    const float off = load_offset<SM>(A.bnb.f.offset);
+    auto mat_of = [&](uint32_t sgi) {  // the weight owning strip group sgi (uniform scan)
+        uint32_t mi = 0;
+        for (uint32_t i = 1; i < A.nmat; ++i) mi = sgi >= A.mat[i].sg_begin ? i : mi;
+        return mi;
+    };
+    uint32_t cmi = 0;  // GRP: the weight of the group being consumed
+    if constexpr (GRP) cmi = mat_of(SPLIT ? blockIdx.x / A.ksplit : blockIdx.x);
+    const float* code2_0 = A.bnb.f.code2;
+    const float* offset_0 = A.bnb.f.offset;
+    if constexpr (GRP) {
+        code2_0 = A.side[cmi].code2;
+        offset_0 = A.side[cmi].offset;
+    }
+    const float c2v = load_code2<SM>(code2_0);
+    float off = load_offset<SM>(offset_0);
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t nl = lane & 15u, kh = lane >> 4;
@@ -1786,6 +1931,7 @@ __global__ __launch_bounds__(64 * W) void nf4_gemm_persist_kernel(const StreamAr
         uint32_t mi = 0;
         for (uint32_t i = 1; i < A.nmat; ++i) mi = sgi >= A.mat[i].sg_begin ? i : mi;
         const StreamMat& Mt = A.mat[mi];
+        if constexpr (GRP && SM == kScaleBnb) g.sh2 = A.side[mi].sh2;
         g.row = ((sgi - Mt.sg_begin) * A.T + strip_in) * 16u + nl;
         g.rw = __builtin_amdgcn_make_buffer_rsrc((void*)Mt.packed, 0, Mt.N * (A.K >> 1), kRsrcFlags);
         g.ra1 = __builtin_amdgcn_make_buffer_rsrc((void*)Mt.a1, 0, Mt.nb_bytes, kRsrcFlags);
@@ -1813,10 +1959,12 @@ __global__ __launch_bounds__(64 * W) void nf4_gemm_persist_kernel(const StreamAr
         } else {
             // one gather per chunk: its nested scale (blocksize2 >= 4: one per chunk), or in
             // single mode the lane's own block scale
+            uint32_t sh2 = 0;
+            if constexpr (SM == kScaleBnb) sh2 = GRP ? gi.sh2 : A.bnb.f.sh2;
 #pragma unroll
             for (int s = 0; s < P; ++s) {
                 const uint32_t q = gi.b2 + P * rr2 + (uint32_t)s;  // the chunk: blocks 4 q .. 4 q + 3
-                const uint32_t i = SM == kScaleBnb ? q >> (A.bnb.f.sh2 - 2u) : 4u * q + kh;
+                const uint32_t i = SM == kScaleBnb ? q >> (sh2 - 2u) : 4u * q + kh;
                 sc.a2[s] = __builtin_amdgcn_raw_buffer_load_b32(gi.ra2, (i * 4u) | oob, 0, 0);
             }
         }
@@ -1950,6 +2098,18 @@ __global__ __launch_bounds__(64 * W) void nf4_gemm_persist_kernel(const StreamAr
             buf ^= 1u;
             rr = 0;
             ++it;
+            if constexpr (GRP && SM == kScaleBnb) {
+                // the next group to consume belongs to another weight: its table and offset
+                // (every wave is past the barrier above, so none reads the old table any more)
+                const uint32_t nmi = it < mine ? mat_of(j0 + it * G) : cmi;
+                if (nmi != cmi) {  // workgroup-uniform
+                    cmi = nmi;
+                    const float v = A.side[nmi].code2[tid & 255u];
+                    off = load_offset<SM>(A.side[nmi].offset);
+                    if (tid < 256u) qtab[tid] = v;
+                    __syncthreads();
+                }
+            }
         }
     };
     for (uint32_t g = 0; g < (NF4_ABL_LOOP_ON ? total : 0u); g += 2) {

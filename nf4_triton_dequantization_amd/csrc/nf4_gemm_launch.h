@@ -38,16 +38,34 @@ int launch_k128_bnb(const HostMat* mats, int count, const void* x, int64_t M, in
 int launch_gemv_bnb(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
                     const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st);
 
+// ... and with the grouped form of those modes (2 to NF4DQ_GEMM_GROUP_MAX weights, all nested
+// or all single, each with its own code2, offset and block sizes), for the families that have
+// it (bnb_grouped_has_mode): the launcher source compiled a third time with NF4_GEMM_BNBG
+// defined (nf4_gemm_launch_*_bnbg.hip).
+int launch_persist_bnbg(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
+                        const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st);
+int launch_xr_bnbg(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
+                   const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st);
+int launch_k128_bnbg(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
+                     const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st);
+
 }  // namespace nf4gemm
 
 // What a launcher source defines and instantiates: launch_<family> with the reference
-// scale mode, or launch_<family>_bnb with the two bitsandbytes modes.
-#ifdef NF4_GEMM_BNB
+// scale mode, launch_<family>_bnb with the two bitsandbytes modes, or launch_<family>_bnbg
+// with their grouped form (the kernels' GRP flag, the longer argument struct).
+#if defined(NF4_GEMM_BNBG)
+#define NF4_GEMM_FN(name_) name_##_bnbg
+#define NF4_GEMM_MODES nf4gemm::kScaleBnb, nf4gemm::kScaleBnbSingle
+#define NF4_GEMM_GRP true
+#elif defined(NF4_GEMM_BNB)
 #define NF4_GEMM_FN(name_) name_##_bnb
 #define NF4_GEMM_MODES nf4gemm::kScaleBnb, nf4gemm::kScaleBnbSingle
+#define NF4_GEMM_GRP false
 #else
 #define NF4_GEMM_FN(name_) name_
 #define NF4_GEMM_MODES nf4gemm::kScaleRef
+#define NF4_GEMM_GRP false
 #endif
 
 namespace {
@@ -97,6 +115,17 @@ inline void fill_mode(Args& a, const HostMat& h) {
 
 inline void fill_mode(StreamArgs& a, const HostMat& h) {  // over the unused second weight's slot
     a.bnb.f = BnbFields{h.code2, h.offset, (uint32_t)h.sh, (uint32_t)h.sh2};
+}
+
+// The mode fields of a launch: launch-wide (one weight), or (GRP) every weight's own.
+template <bool GRP, class Args>
+inline void fill_modes(Args& a, const HostMat* mats, int count) {
+    if constexpr (GRP) {
+        for (int i = 0; i < count; ++i)
+            a.side[i] = BnbSide{mats[i].code2, mats[i].offset, (uint32_t)mats[i].sh, (uint32_t)mats[i].sh2};
+    } else {
+        if (count > 0) fill_mode(a, mats[0]);
+    }
 }
 
 // One weight's pointers, N and absmax divisors.  The divisors are clamped, nb at 2^31

@@ -9,7 +9,7 @@ namespace nf4gemm {
 int NF4_GEMM_FN(launch_k128)(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
                 const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st) {
     const int nt = cfg.strips > 1 ? cfg.strips : 1;  // 16-column strips per wave
-    GemmArgs A{};
+    GemmArgsOf<NF4_GEMM_GRP> A{};
     fill_common(A, count, x, M, K, cfg, workspace);
     A.chunks = (uint32_t)(K / kChunkK);
     A.chunks_per_split = (A.chunks + A.ksplit - 1) / A.ksplit;
@@ -24,7 +24,7 @@ int NF4_GEMM_FN(launch_k128)(const HostMat* mats, int count, const void* x, int6
     }
     A.col_groups = cgs;
     A.ncols = cols;
-    if (count > 0) fill_mode(A, mats[0]);
+    fill_modes<NF4_GEMM_GRP>(A, mats, count);
     const LaunchShape ls = launch_shape(cfg, M, K, mats, count, cus);
     const bool vs = ls.dyn != 0;  // the scale table in LDS: the vector-scale form
     const dim3 grid(ls.grid), block(ls.block);
@@ -36,8 +36,8 @@ int NF4_GEMM_FN(launch_k128)(const HostMat* mats, int count, const void* x, int6
                     pick<8, 4>(cfg.waves, [&](auto W) {
                         pick<4, 2, 1>(nt, [&](auto NT) {
                             pick<NF4_GEMM_MODES>(count > 0 ? mats[0].mode : kScaleRef, [&](auto SM) {
-                                constexpr auto scales_in_lds = &nf4_gemm_smallm_kernel<DT, MT, D, W, NT, true, SM>;
-                                constexpr auto scales_gathered = &nf4_gemm_smallm_kernel<DT, MT, D, W, NT, false, SM>;
+                                constexpr auto scales_in_lds = &nf4_gemm_smallm_kernel<DT, MT, D, W, NT, true, SM, NF4_GEMM_GRP>;
+                                constexpr auto scales_gathered = &nf4_gemm_smallm_kernel<DT, MT, D, W, NT, false, SM, NF4_GEMM_GRP>;
                                 if (vs) hipLaunchKernelGGL(scales_in_lds, grid, block, ls.dyn, st, A);
                                 else hipLaunchKernelGGL(scales_gathered, grid, block, 0, st, A);
                                 rc = hip_rc2(hipGetLastError());

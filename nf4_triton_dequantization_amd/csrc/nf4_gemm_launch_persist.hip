@@ -8,7 +8,7 @@ namespace nf4gemm {
 // validated per weight and known to run: cfg_runs).  Grid: persist_grid.
 int NF4_GEMM_FN(launch_persist)(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
                    const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st) {
-    StreamArgs S{};
+    StreamArgsOf<NF4_GEMM_GRP> S{};
     fill_common(S, count, x, M, K, cfg, workspace);
     S.T = (uint32_t)cfg.strips;
     S.parts = (uint32_t)(cfg.waves / cfg.strips);
@@ -30,7 +30,7 @@ int NF4_GEMM_FN(launch_persist)(const HostMat* mats, int count, const void* x, i
     }
     S.sg_total = sg;
     S.ncols = strips * 16u;
-    if (count == 1 && mats[0].mode != kScaleRef) fill_mode(S, mats[0]);
+    if (NF4_GEMM_GRP || (count == 1 && mats[0].mode != kScaleRef)) fill_modes<NF4_GEMM_GRP>(S, mats, count);
     if (cfg_runs(cfg, M, K, mats, count, cus) != NF4DQ_OK) return NF4DQ_ERR_ARG;  // not a plan
     const PersistGrid g = persist_grid(M, K, cfg, sg, cus);
     S.zero_off = g.zero_off;
@@ -42,7 +42,7 @@ int NF4_GEMM_FN(launch_persist)(const HostMat* mats, int count, const void* x, i
             pick<2, 4>(cfg.depth, [&](auto P) {
                 pick<true, false>(S.ksplit > 1, [&](auto SPLIT) {
                     pick<NF4_GEMM_MODES>(count > 0 ? mats[0].mode : kScaleRef, [&](auto SM) {
-                        launch_lds<&nf4_gemm_persist_kernel<DT, W, P, SPLIT, SM>>(kStreamLdsCap, grid, block, g.dyn, st,
+                        launch_lds<&nf4_gemm_persist_kernel<DT, W, P, SPLIT, SM, NF4_GEMM_GRP>>(kStreamLdsCap, grid, block, g.dyn, st,
                                                                                    S);
                     });
                 });

@@ -6,7 +6,7 @@ namespace nf4gemm {
 
 int NF4_GEMM_FN(launch_xr)(const HostMat* mats, int count, const void* x, int64_t M, int64_t K, int32_t dtype,
               const nf4_gemm_cfg& cfg, void* workspace, int cus, hipStream_t st) {
-    GemmArgs A{};
+    GemmArgsOf<NF4_GEMM_GRP> A{};
     fill_common(A, count, x, M, K, cfg, workspace);
     A.chunks = (uint32_t)(K / kChunkK);
     A.chunks_per_split = (uint32_t)(cfg.waves * cfg.strips);
@@ -20,8 +20,9 @@ int NF4_GEMM_FN(launch_xr)(const HostMat* mats, int count, const void* x, int64_
     }
     A.col_groups = strips;
     A.ncols = strips * 16u;
-    if (count > 0) fill_mode(A, mats[0]);
-    A.per_wg = xr_per_wg(M, strips, cfg, cus, count > 0 ? mats[0].mode : kScaleRef);
+    fill_modes<NF4_GEMM_GRP>(A, mats, count);
+    A.per_wg = xr_per_wg(M, strips, cfg, cus, count > 0 ? mats[0].mode : kScaleRef,
+                         count > 0 ? group_tables(mats, count) : 0);
     const LaunchShape ls = launch_shape(cfg, M, K, mats, count, cus);
     const uint32_t ks = A.ksplit, lds = ls.dyn;
     const dim3 grid(ls.grid), block(ls.block);
@@ -43,8 +44,8 @@ int NF4_GEMM_FN(launch_xr)(const HostMat* mats, int count, const void* x, int64_
                                     pick<NF4_GEMM_MODES>(count > 0 ? mats[0].mode : kScaleRef, [&](auto SM) {
                                         const uint32_t cap = kLdsPerCu - xr_lds_static(KPW, SM);
                                         // both templates are instantiated for every GU, as ever
-                                        constexpr auto xrg = &nf4_gemm_xrg_kernel<DT, MT, W, KPW, D, GU, SM>;
-                                        constexpr auto xr = &nf4_gemm_xr_kernel<DT, MT, W, KPW, D, GU, SM>;
+                                        constexpr auto xrg = &nf4_gemm_xrg_kernel<DT, MT, W, KPW, D, GU, SM, NF4_GEMM_GRP>;
+                                        constexpr auto xr = &nf4_gemm_xr_kernel<DT, MT, W, KPW, D, GU, SM, NF4_GEMM_GRP>;
                                         if (GU) launch_lds<xrg>(cap, grid, block, lds, st, A);
                                         else launch_lds<xr>(cap, grid, block, lds, st, A);
                                         rc = hip_rc2(hipGetLastError());

@@ -74,6 +74,12 @@ inline bool no_wrap_in_row(const HostMat* mats, int count, int64_t K) {
     return true;
 }
 
+// code2 tables a launch keeps in LDS beside its usual ones: one per weight in a grouped
+// nested bitsandbytes launch of the register-resident kernel (nf4_gemm_bnb_grouped), else 0.
+inline int group_tables(const HostMat* mats, int count) {
+    return count > 1 && mats[0].mode == kScaleBnb ? count : 0;
+}
+
 // ---- launch geometry, per family ---------------------------------------------
 struct StreamPlan {
     uint32_t cps, xstride, zero_off, red_off, lds;
@@ -153,21 +159,24 @@ inline uint32_t xs_lds_bytes(int64_t M, int kc, int waves) {
 constexpr uint32_t xr_lds_static(int kpw, int mode = kScaleRef) {  // pair table + q/127 or code2, static in the kernel
     return kpw >= 2 ? 256u * 32u * 8u + 1024u : mode == kScaleBnb ? 64u + 1024u : 64u;
 }
-inline uint32_t xr_lds_dynamic(int64_t M, int waves, uint32_t T) {
+// (tables: group_tables -- each weight's code2 and, in 32 bytes after them, the offsets)
+inline uint32_t xr_lds_dynamic(int64_t M, int waves, uint32_t T, int tables = 0) {
     const uint32_t mt = M > 16 ? 2u : 1u;
     const uint32_t r = waves == 8 ? 2u : 1u;  // strips per reduction group (kernel's R; depth is even)
-    return 2u * r * (uint32_t)waves * mt * 1024u + 64u + 256u + T * mt * 1024u;  // partials, codes, flags, held
+    const uint32_t tab = tables > 0 ? (uint32_t)tables * 1024u + 32u : 0u;
+    return 2u * r * (uint32_t)waves * mt * 1024u + 64u + 256u + T * mt * 1024u + tab;  // partials, codes, flags, held
 }
-inline uint32_t xr_lds_bytes(int64_t M, int waves, int kpw, uint32_t T, int mode = kScaleRef) {
-    return xr_lds_static(kpw, mode) + xr_lds_dynamic(M, waves, T);
+inline uint32_t xr_lds_bytes(int64_t M, int waves, int kpw, uint32_t T, int mode = kScaleRef, int tables = 0) {
+    return xr_lds_static(kpw, mode) + xr_lds_dynamic(M, waves, T, tables);
 }
 
-inline uint32_t xr_per_wg(int64_t M, int64_t strips, const nf4_gemm_cfg& c, int cus, int mode = kScaleRef) {
+inline uint32_t xr_per_wg(int64_t M, int64_t strips, const nf4_gemm_cfg& c, int cus, int mode = kScaleRef,
+                          int tables = 0) {
     const uint32_t wg_per_cu = c.waves == 16 || c.strips >= 2 ? 1u : 2u;  // the pair table leaves room for one
     uint32_t P = (uint32_t)cus * wg_per_cu / (uint32_t)c.ksplit;          // workgroups per K slice
     if (P < 1) P = 1;
     uint32_t T = (uint32_t)((strips + P - 1) / P);
-    while (T > 1 && (T > 64 || xr_lds_bytes(M, c.waves, c.strips, T, mode) > kLdsPerCu)) T = (T + 1) / 2;
+    while (T > 1 && (T > 64 || xr_lds_bytes(M, c.waves, c.strips, T, mode, tables) > kLdsPerCu)) T = (T + 1) / 2;
     return T < 1 ? 1u : T;
 }
 
@@ -217,9 +226,10 @@ inline LaunchShape launch_shape(const nf4_gemm_cfg& c, int64_t M, int64_t K, con
             l.dyn = xs_lds_bytes(M, c.depth, c.waves);
             break;
         case NF4DQ_GEMM_XR: {
-            const uint32_t per_wg = xr_per_wg(M, rows / 16u, c, cus, count > 0 ? mats[0].mode : kScaleRef);
+            const int tables = count > 0 ? group_tables(mats, count) : 0;
+            const uint32_t per_wg = xr_per_wg(M, rows / 16u, c, cus, count > 0 ? mats[0].mode : kScaleRef, tables);
             l.grid = (rows / 16u + per_wg - 1) / per_wg * ks;
-            l.dyn = xr_lds_dynamic(M, c.waves, per_wg);
+            l.dyn = xr_lds_dynamic(M, c.waves, per_wg, tables);
             break;
         }
         case NF4DQ_GEMM_K128: {
@@ -526,6 +536,79 @@ inline size_t bnb_library_workspace(int64_t M, int64_t N, int64_t K) {
     for (const nf4_gemm_cfg& c : cs) {
         const size_t wc = bnb_has_mode(c.kernel) ? workspace_need(M, N, K, c) : 0;
         w = wc > w ? wc : w;
+    }
+    return w;
+}
+
+// ---- grouped bitsandbytes semantics (nf4_gemm_bnb_grouped) -----------------------
+// The families with the grouped form of the bnb modes: the ones the reference grouped plan
+// chooses for model shapes (persistent, register-resident) and the 128-deep catch-all.  The
+// decode GEMV, the streaming and the shared-activation kernels do not have it.
+inline bool bnb_grouped_has_mode(int kernel) {
+    return kernel == NF4DQ_GEMM_K128 || kernel == NF4DQ_GEMM_XR || kernel == NF4DQ_GEMM_PERSIST;
+}
+// A cfg can take the group: a family with the grouped mode; above blocksize 64 (sh > 0 in
+// any weight) the 128-deep kernel alone.
+inline bool bnb_grouped_cfg_ok(const nf4_gemm_cfg& c, const HostMat* mats, int count) {
+    if (!bnb_grouped_has_mode(c.kernel)) return false;
+    for (int i = 0; i < count; ++i)
+        if (mats[i].sh != 0 && c.kernel != NF4DQ_GEMM_K128) return false;
+    return true;
+}
+
+// What a grouped bnb call runs without a cfg: ONE launch over the column total -- the
+// reference grouped plan's (same family, same decomposition) where that family has the
+// grouped mode and every weight has blocksize 64; the persistent kernel where the reference
+// plan picks the decode GEMV (its choice there before the GEMV existed: default_gemm_cfg);
+// the 128-deep substitute (k128_tail_cfg of the column total) where it picks the streaming
+// or shared-activation kernel or a weight has a larger blocksize.  Only where the persistent
+// cfg cannot run (cfg_runs) every weight gets bnb_choice's launch of its own (per_weight).
+inline Choice bnb_grouped_choice(int64_t M, int64_t K, const HostMat* mats, int count, int cus) {
+    int64_t ntot = 0;
+    bool empty = false;
+    for (int i = 0; i < count; ++i) {
+        ntot += mats[i].N;
+        empty = empty || mats[i].N == 0;
+    }
+    const Choice ref = library_choice(M, K, mats, count, cus);
+    nf4_gemm_cfg c = ref.cfg.kernel == NF4DQ_GEMM_GEMV ? ref.first : ref.cfg;
+    if (ref.cfg.kernel == NF4DQ_GEMM_GEMV && c.kernel != NF4DQ_GEMM_PERSIST) {
+        // K / 256 chunks do not split over 8 waves' rings (K = 2048, 14336): 4 waves' do
+        const nf4_gemm_cfg p4{NF4DQ_GEMM_PERSIST, 4, 2, 1, 1};
+        if (valid_gemm_cfg(p4, M, 64, K)) c = p4;
+    }
+    bool ok = bnb_grouped_cfg_ok(c, mats, count) && !(empty && !takes_empty_weight(c.kernel));
+    for (int i = 0; i < count && ok; ++i) ok = mats[i].N == 0 || valid_gemm_cfg(c, M, mats[i].N, K);
+    if (!ok) c = k128_tail_cfg(M, ntot, K);
+    Choice ch{c, c, false};
+    ch.per_weight = c.kernel == NF4DQ_GEMM_PERSIST && cfg_runs(c, M, K, mats, count, cus) != NF4DQ_OK;
+    return ch;
+}
+
+// What nf4_gemm_bnb_grouped_workspace_bytes answers: a named cfg's need over the column
+// total; without one (the CU count is not known here) the largest need of what
+// bnb_grouped_choice can come to, the per-weight fallback's launches included.
+template <class Mat>
+inline size_t bnb_grouped_workspace(int64_t M, int64_t K, const Mat* mats, int count, const nf4_gemm_cfg* cfgp) {
+    if (count <= 0 || count > kGroupMax || !mats || M <= 0 || K <= 0 || K % kChunkK) return 0;
+    int64_t ntot = 0;
+    for (int i = 0; i < count; ++i) {
+        if (mats[i].N < 0 || mats[i].N % 64) return 0;
+        ntot += mats[i].N;
+    }
+    if (ntot <= 0) return 0;
+    if (cfgp) {
+        nf4_gemm_cfg cfg = *cfgp;
+        if (cfg.kernel == 0) cfg.kernel = default_gemm_cfg(M, ntot, K).kernel;
+        return workspace_need(M, ntot, K, cfg);
+    }
+    size_t w = workspace_need(M, ntot, K, k128_tail_cfg(M, ntot, K));
+    const nf4_gemm_cfg d = default_gemm_cfg(M, ntot, K);
+    const size_t wd = bnb_grouped_has_mode(d.kernel) ? workspace_need(M, ntot, K, d) : 0;
+    w = wd > w ? wd : w;
+    for (int i = 0; i < count; ++i) {
+        const size_t wi = bnb_library_workspace(M, mats[i].N, K);
+        w = wi > w ? wi : w;
     }
     return w;
 }

@@ -685,3 +685,98 @@ def nf4_linear_grouped(x: torch.Tensor, modules: Sequence, biases: Optional[Sequ
             y = y + b.to(y.dtype)
         out.append(y.reshape(*lead, m))
     return out
+
+
+def _bnb_nested(qs) -> bool:
+    """Nested statistics or plain fp32 absmax, decided as ``_launch_bnb`` and ``nf4_linear_bnb`` do."""
+    return getattr(qs, "state2", None) is not None and qs.absmax.dtype == torch.uint8
+
+
+def nf4_linear_bnb_grouped(x: torch.Tensor, modules: Sequence,
+                           biases: Optional[Sequence] = None) -> List[torch.Tensor]:
+    """``[x @ W_i.t() (+ b_i)]`` for ``Linear4bit`` weights W_i in bitsandbytes semantics that
+    share the input x (q/k/v, gate/up): what ``nf4_linear_bnb`` gives per weight, in ONE fused
+    launch (``nf4_gemm_bnb_grouped``).
+
+    The fused launch is taken when there are more than one and at most ``GEMM_GROUP_MAX``
+    modules, every module meets ``nf4_linear_bnb``'s fused-path rules, all share
+    ``in_features``, ``quant_state.dtype`` and the device, all have nested statistics or all
+    plain fp32 ``absmax``, and no gradient is being recorded for ``x``.  Each weight keeps its
+    own ``code2`` table, ``offset`` (read on the device: the call never synchronises with the
+    host), ``blocksize`` and ``blocksize2``.  Otherwise every module goes through
+    ``nf4_linear_bnb``, which keeps autograd and every odd shape working.  The weights are the
+    same bit for bit on both routes; the summation order may differ.
+    """
+    modules = list(modules)
+    biases = list(biases) if biases is not None else [None] * len(modules)
+    if len(biases) != len(modules):
+        raise ValueError("nf4_linear_bnb_grouped: one bias (or None) per module")
+    if not modules:
+        return []
+    K = int(modules[0].in_features)
+    lead = x.shape[:-1]
+    M = x.numel() // K if K and x.shape[-1] == K else 0
+    qs0 = modules[0].weight.quant_state
+    dtype, dev = qs0.dtype, modules[0].weight.data.device
+    nested = _bnb_nested(qs0)
+    grouped = (1 < len(modules) <= _lib.GEMM_GROUP_MAX and dev.type == "cuda" and x.device == dev
+               and dtype in (torch.float16, torch.bfloat16) and 0 < M <= _lib.GEMM_MAX_M and K % 128 == 0
+               and not (torch.is_grad_enabled() and x.requires_grad))
+    for mod in modules:
+        if not grouped:
+            break
+        q, qs, N = mod.weight.data, mod.weight.quant_state, int(mod.out_features)
+        grouped = (int(mod.in_features) == K and qs.dtype == dtype and q.device == dev and N % 64 == 0
+                   and q.dtype == torch.uint8 and q.numel() == N * K // 2
+                   and getattr(qs, "quant_type", None) == "nf4" and _bnb_gemm_blocksizes(qs)
+                   and _bnb_nested(qs) == nested)
+    if not grouped:
+        return [nf4_linear_bnb(x, mod, b) for mod, b in zip(modules, biases)]
+    xc = x.reshape(M, K)
+    if xc.dtype != dtype:
+        xc = xc.to(dtype)
+    xc = xc.contiguous()
+    ys, keep = [], []  # keep: every temporary outlives the enqueue (the caching allocator reuses freed blocks)
+    mats = (_lib.GemmBnbMat * len(modules))()
+    with torch.cuda.device(dev):
+        for i, mod in enumerate(modules):
+            q, qs, N = mod.weight.data, mod.weight.quant_state, int(mod.out_features)
+            y = torch.empty((M, N), dtype=dtype, device=dev)
+            qc, qp, qn = _flat_ptr(q)
+            if nested:
+                _on_device(dev, qs.absmax, qs.state2.code, qs.state2.absmax)
+                a1, ap, an = _flat_ptr(qs.absmax)
+                c2 = qs.state2.code
+                c2, cp, cn = _flat_ptr(c2 if c2.dtype == torch.float32 else c2.to(torch.float32))
+                a2 = qs.state2.absmax
+                a2, bp, bn = _flat_ptr(a2 if a2.dtype == torch.float32 else a2.to(torch.float32))
+                if cn != 256:
+                    raise RuntimeError(f"nf4_linear_bnb_grouped: state2.code has {cn} entries, expected 256")
+                off, op = _offset_ptr(qs.offset, dev)
+                keep.extend((qc, a1, c2, a2, off))
+                mats[i] = _lib.GemmBnbMat(qp, qn, ap, an, cp, bp, bn, op, int(qs.blocksize),
+                                          int(qs.state2.blocksize), y.data_ptr(), N)
+            else:
+                _on_device(dev, qs.absmax)
+                am = qs.absmax
+                am, ap, an = _flat_ptr(am if am.dtype == torch.float32 else am.to(torch.float32))
+                keep.extend((qc, am))
+                mats[i] = _lib.GemmBnbMat(qp, qn, None, 0, None, ap, an, None, int(qs.blocksize), 0,
+                                          y.data_ptr(), N)
+            ys.append(y)
+        L = _lib.lib()
+        mp = ctypes.cast(mats, ctypes.c_void_p)
+        single = 0 if nested else 1
+        ws_bytes = L.nf4_gemm_bnb_grouped_workspace_bytes(M, K, mp, len(modules), single, None)
+        ws = _gemm_workspace(dev, ws_bytes) if ws_bytes else None
+        rc = L.nf4_gemm_bnb_grouped(xc.data_ptr(), M, K, mp, len(modules), single, _dtype_code(dtype),
+                                    ws.data_ptr() if ws is not None else None, ws_bytes, None,
+                                    torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "nf4 fused grouped bnb gemm")
+    del keep
+    out = []
+    for y, b, mod in zip(ys, biases, modules):
+        if b is not None:
+            y = y + b.to(y.dtype)
+        out.append(y.reshape(*lead, int(mod.out_features)))
+    return out

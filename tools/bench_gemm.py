@@ -25,6 +25,12 @@ rotation of distinct weights larger than the Infinity Cache, and then the whole 
   forward    Linear4bit.forward (nf4_linear_bnb: one fused launch), eager, wall clock
   unfused    what forward did before: dequantize_nf4_bnb (host read of the offset) + matmul,
              eager, wall clock
+  grouped    (the pass only) nf4_gemm_bnb_grouped: q/k/v in one launch, gate/up in one, o and
+             down through nf4_gemm_bnb -- 128 launches -- replayed in turn with the per-weight
+             bnb pass (224 launches, from ``--parent-lib`` when given: another build of the
+             library loaded beside this one), with a second capture of that per-weight pass
+             (the spread of a pass against itself) and with the reference-mode grouped pass
+             (nf4_gemm_ref_grouped on the same bytes: a yardstick)
 
 One JSON line per (shape, M) with medians, min - max of the rounds and the ratios.
 """
@@ -82,11 +88,11 @@ def _wall_us(fn, n, reps=3):
     return ts[len(ts) // 2]
 
 
-def _interleaved_us(fa, fb, n, rounds=5):
-    """fa and fb (n launches each) captured once, replayed in turn; per-launch microseconds
-    of every round."""
+def _interleaved_rounds(fns, n, rounds=5):
+    """Each of fns (n launches each) captured once, replayed in turn; per-launch microseconds
+    of every round, in round order (entry r of every list belongs to the same round)."""
     graphs = []
-    for fn in (fa, fb):
+    for fn in fns:
         fn()
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
@@ -96,7 +102,7 @@ def _interleaved_us(fa, fb, n, rounds=5):
         graphs.append(g)
     torch.cuda.synchronize()
     st = torch.cuda.current_stream()
-    out = ([], [])
+    out = [[] for _ in fns]
     for _ in range(rounds):
         for g, ts in zip(graphs, out):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -105,7 +111,13 @@ def _interleaved_us(fa, fb, n, rounds=5):
             e1.record(st)
             torch.cuda.synchronize()
             ts.append(e0.elapsed_time(e1) * 1e3 / n)
-    return [sorted(t) for t in out]
+    return out
+
+
+def _interleaved_us(fa, fb, n, rounds=5):
+    """fa and fb (n launches each) captured once, replayed in turn; per-launch microseconds
+    of every round."""
+    return [sorted(t) for t in _interleaved_rounds((fa, fb), n, rounds)]
 
 
 def _stats(ts):
@@ -176,6 +188,96 @@ def main_bnb(args):
             res["ref_pass_ms"] = round(tr[len(tr) // 2] * len(mods) / 1e3, 4)
         print(json.dumps(res), flush=True)
 
+    def measure_grouped(mods, M):
+        """The pass with q/k/v and gate/up grouped (128 launches) against the per-weight pass."""
+        Lp = L
+        if args.parent_lib:
+            import ctypes
+
+            Lp = ctypes.CDLL(os.path.join(REPO, "tools", "_build", f"libnf4dq_{args.parent_lib}.so"))
+            for name in ("nf4_gemm_bnb", "nf4_gemm_bnb_workspace_bytes"):
+                getattr(Lp, name).restype, getattr(Lp, name).argtypes = _lib.SIGNATURES[name]
+        K = 4096
+        x = {k: torch.randn((M, k), device=dev, generator=gen).to(torch.bfloat16) for k in {m.in_features for m in mods}}
+        ys = [torch.empty((M, m.out_features), dtype=torch.bfloat16, device=dev) for m in mods]
+        t = []
+        for m in mods:
+            qs = m.weight.quant_state
+            t.append((m.weight.data, qs.absmax, qs.state2.code, qs.state2.absmax, qs.offset))
+        import ctypes
+
+        plan, keep = [], []  # (in_features, bnb mats or None, ref mats or None, count, module index)
+        for b in range(0, len(mods), len(SHAPES)):
+            for idx in ((0, 1, 2), (3,), (4, 5), (6,)):
+                if len(idx) == 1:
+                    plan.append((mods[b + idx[0]].in_features, None, None, 1, b + idx[0]))
+                    continue
+                bm, rm = (_lib.GemmBnbMat * len(idx))(), (_lib.GemmMat * len(idx))()
+                for j, i in enumerate(idx):
+                    q, a1, c2, a2, off = t[b + i]
+                    n = mods[b + i].out_features
+                    bm[j] = _lib.GemmBnbMat(q.data_ptr(), q.numel(), a1.data_ptr(), a1.numel(), c2.data_ptr(),
+                                            a2.data_ptr(), a2.numel(), off.data_ptr(), 64, 256, ys[b + i].data_ptr(), n)
+                    rm[j] = _lib.GemmMat(q.data_ptr(), q.numel(), a1.data_ptr(), a1.numel(), a2.data_ptr(), a2.numel(),
+                                         ys[b + i].data_ptr(), n)
+                keep.append((bm, rm))
+                plan.append((K, ctypes.cast(bm, ctypes.c_void_p), rm, len(idx), b + idx[0]))
+        wsz = max(max(L.nf4_gemm_bnb_workspace_bytes(M, m.out_features, m.in_features, None),
+                      Lp.nf4_gemm_bnb_workspace_bytes(M, m.out_features, m.in_features, None),
+                      L.nf4_gemm_workspace_bytes(M, m.out_features, m.in_features)) for m in mods)
+        for (k, bm, rm, c, _i) in plan:
+            if c > 1:
+                wsz = max(wsz, L.nf4_gemm_bnb_grouped_workspace_bytes(M, k, bm, c, 0, None),
+                          L.nf4_gemm_grouped_workspace_bytes(M, k, rm, c, None))
+        work = torch.zeros(max(wsz, 1 << 16), dtype=torch.uint8, device=dev)
+
+        def one(lib, i, sp):
+            m, (q, a1, c2, a2, off) = mods[i], t[i]
+            rc = lib.nf4_gemm_bnb(x[m.in_features].data_ptr(), M, q.data_ptr(), q.numel(), a1.data_ptr(), a1.numel(),
+                                  c2.data_ptr(), a2.data_ptr(), a2.numel(), off.data_ptr(), 64, 256, ys[i].data_ptr(),
+                                  _lib.BF16, m.out_features, m.in_features, work.data_ptr(), wsz, None, sp)
+            assert rc == 0, rc
+
+        def per_weight():
+            sp = torch.cuda.current_stream().cuda_stream
+            for i in range(len(mods)):
+                one(Lp, i, sp)
+
+        def grouped():
+            sp = torch.cuda.current_stream().cuda_stream
+            for (k, bm, _rm, c, i) in plan:
+                if c == 1:
+                    one(L, i, sp)
+                else:
+                    rc = L.nf4_gemm_bnb_grouped(x[k].data_ptr(), M, k, bm, c, 0, _lib.BF16, work.data_ptr(), wsz, None, sp)
+                    assert rc == 0, rc
+
+        def ref_grouped():
+            sp = torch.cuda.current_stream().cuda_stream
+            for (k, _bm, rm, c, i) in plan:
+                if c == 1:
+                    m, (q, a1, _c2, a2, _off) = mods[i], t[i]
+                    rc = L.nf4_gemm_ref(x[m.in_features].data_ptr(), M, q.data_ptr(), q.numel(), a1.data_ptr(),
+                                        a1.numel(), a2.data_ptr(), a2.numel(), ys[i].data_ptr(), _lib.BF16,
+                                        m.out_features, m.in_features, work.data_ptr(), wsz, sp)
+                else:
+                    rc = L.nf4_gemm_ref_grouped(x[k].data_ptr(), M, k, rm, c, _lib.BF16, work.data_ptr(), wsz, None, sp)
+                assert rc == 0, rc
+
+        pa, gr, pb, rg = _interleaved_rounds((per_weight, grouped, per_weight, ref_grouped), 1, args.rounds)
+        assert L.nf4_gemm_check_workspace(work.data_ptr(), wsz, torch.cuda.current_stream().cuda_stream) == 0
+        med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+        self_spread = max(abs(a / b - 1.0) for a, b in zip(pa, pb))
+        gain = [a / g - 1.0 for a, g in zip(pa, gr)]
+        print(json.dumps({"semantics": "bnb", "what": "grouped", "M": M, "launches": len(plan),
+                          "per_weight_launches": len(mods), "per_weight_lib": args.parent_lib or "this",
+                          "per_weight_pass_us": _stats(sorted(pa)), "per_weight_again_pass_us": _stats(sorted(pb)),
+                          "grouped_pass_us": _stats(sorted(gr)), "ref_grouped_pass_us": _stats(sorted(rg)),
+                          "per_weight_over_grouped": round(med(pa) / med(gr), 4),
+                          "gain_per_round_min": round(min(gain), 4), "self_pair_spread_max": round(self_spread, 4),
+                          "faster_by_more_than_the_spread": bool(min(gain) > self_spread),
+                          "grouped_over_ref_grouped": round(med(gr) / med(rg), 4)}), flush=True)
+
     ms = [int(v) for v in args.ms.split(",")]
     for sh in [s for s in args.shapes.split(";") if s]:
         n, k = (int(v) for v in sh.split(","))
@@ -187,7 +289,9 @@ def main_bnb(args):
     if args.layers > 0:
         mods = [quantized(n, k) for _ in range(args.layers) for (n, k) in SHAPES]
         for M in ms:
-            measure("pass", mods, M)
+            if not args.grouped_only:
+                measure("pass", mods, M)
+            measure_grouped(mods, M)
 
 
 def main():
@@ -196,6 +300,9 @@ def main():
     ap.add_argument("--shapes", default="4096,4096;14336,4096;4096,14336", help="--semantics bnb: N,K;N,K;...")
     ap.add_argument("--budget-mb", type=int, default=768, help="--semantics bnb: packed bytes of a shape's rotation")
     ap.add_argument("--rounds", type=int, default=5, help="--semantics bnb: interleaved replay pairs")
+    ap.add_argument("--parent-lib", default="", help="--semantics bnb: tools/_build/libnf4dq_<name>.so whose "
+                    "nf4_gemm_bnb runs the per-weight side of the grouped row")
+    ap.add_argument("--grouped-only", action="store_true", help="--semantics bnb: of the pass, only the grouped row")
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--ms", default="1,4,8,16,32")
     ap.add_argument("--no-bf16", action="store_true")
