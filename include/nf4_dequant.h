@@ -124,6 +124,54 @@ int nf4_dequant_bnb_single(const uint8_t* packed, const float* absmax, int64_t n
                            void* out, int32_t out_dtype, int64_t numel,
                            int32_t blocksize, void* hip_stream);
 
+/* Embedding lookup from an NF4 table in bitsandbytes semantics (bnb.nn.Embedding4bit):
+ * the weight is the flat stream nf4_dequant_bnb reads, viewed as [rows][dim], and
+ *   out[i][j] = the value nf4_dequant_bnb / nf4_dequant_bnb_single writes for element
+ *               ids[i] * dim + j, bit for bit (fp16 / bf16 / fp32 `out_dtype`),
+ * for i < count: out is a dense [count][dim].  Only the selected rows' packed bytes and
+ * statistics are read.  A row is not a unit of the layout: any dim >= 1 is taken (statistics
+ * blocks may span rows, odd rows of an odd dim start on a low nibble); dim % 64 == 0 with
+ * `packed` 4-byte and `out` 16-byte aligned runs the fast kernel, anything else an exact
+ * one-thread-per-element kernel.
+ *   ids     int32 (NF4DQ_IDS_I32) or int64 (NF4DQ_IDS_I64) [count], on the device.
+ *           Out-of-range rule: an id outside [0, rows), compared in its own signed type,
+ *           gives a row of zero bits and reads nothing from the table -- no device assert,
+ *           no out-of-bounds read, no host check (which would synchronise).
+ *   offset  ONE fp32 ON THE DEVICE, read when the kernel runs (no host copy, no
+ *           synchronisation; it may change between calls); NULL = 0.  As nf4_gemm_bnb.
+ *   code2   256 fp32 on the device.
+ * blocksize: a power of two, 64..4096; blocksize2: a power of two >= 4; a bad ids_dtype /
+ * out_dtype / block size, or a null ids / packed / statistics / out with count > 0:
+ * NF4DQ_ERR_ARG (so is a pointer not aligned to its element).  A negative count / rows /
+ * dim / nb / n2, dim < 1 with count > 0, nb (nabs) < ceil(rows*dim / blocksize) or n2 <
+ * ceil(that / blocksize2): NF4DQ_ERR_SHAPE.  count == 0: NF4DQ_OK, nothing launched.
+ * Too-large rule: a call is one launch that indexes its output with 32 bits, so count * dim
+ * > 2^31 - 1 is NF4DQ_ERR_TOO_LARGE (never split into several launches; the caller splits
+ * `ids`), and so is a table of more than 2^62 elements.
+ * One launch on `hip_stream`, no allocation, no read-back: capturable in a graph. */
+#define NF4DQ_IDS_I32 0
+#define NF4DQ_IDS_I64 1
+int nf4_embedding_bnb(const void* ids, int32_t ids_dtype, int64_t count,
+                      const uint8_t* packed, const uint8_t* absmax_q, int64_t nb, const float* code2,
+                      const float* absmax2, int64_t n2, const float* offset,
+                      int32_t blocksize, int32_t blocksize2,
+                      void* out, int32_t out_dtype, int64_t rows, int64_t dim, void* hip_stream);
+int nf4_embedding_bnb_single(const void* ids, int32_t ids_dtype, int64_t count, const uint8_t* packed,
+                             const float* absmax, int64_t nabs, int32_t blocksize,
+                             void* out, int32_t out_dtype, int64_t rows, int64_t dim, void* hip_stream);
+
+/* Host forms: every pointer (`offset` included) is a HOST pointer, the call is synchronous,
+ * `threads` workers split the output rows (<= 0 = all hardware threads); the same results
+ * bit for bit, the same rules and error codes. */
+int nf4_embedding_bnb_cpu(const void* ids, int32_t ids_dtype, int64_t count,
+                          const uint8_t* packed, const uint8_t* absmax_q, int64_t nb, const float* code2,
+                          const float* absmax2, int64_t n2, const float* offset,
+                          int32_t blocksize, int32_t blocksize2,
+                          void* out, int32_t out_dtype, int64_t rows, int64_t dim, int32_t threads);
+int nf4_embedding_bnb_single_cpu(const void* ids, int32_t ids_dtype, int64_t count, const uint8_t* packed,
+                                 const float* absmax, int64_t nabs, int32_t blocksize,
+                                 void* out, int32_t out_dtype, int64_t rows, int64_t dim, int32_t threads);
+
 /* The producer side: quantize a flat stream of `numel` float elements (`in_dtype`:
  * NF4DQ_F16 / NF4DQ_BF16 / NF4DQ_F32 name the INPUT type here) into the layout the
  * nf4_dequant_bnb* entries read.  The specification is the package's Python quantizer

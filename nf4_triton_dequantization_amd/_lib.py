@@ -33,6 +33,8 @@ ERR_SPLITK_TIMEOUT = 4
 ERR_HIP_BASE = 1000
 
 BATCH_MAX = 24
+IDS_I32 = 0
+IDS_I64 = 1
 GEMM_MAX_M = 32
 
 
@@ -113,6 +115,12 @@ SIGNATURES = {
     "nf4_dequant_ref_batched": (ctypes.c_int, [ctypes.POINTER(MatrixDesc), _I32, _I32, _P]),
     "nf4_dequant_bnb": (ctypes.c_int, [_P, _P, _I64, _P, _P, _I64, _F, _P, _I32, _I64, _I32, _I32, _P]),
     "nf4_dequant_bnb_single": (ctypes.c_int, [_P, _P, _I64, _P, _I32, _I64, _I32, _P]),
+    "nf4_embedding_bnb": (ctypes.c_int, [_P, _I32, _I64, _P, _P, _I64, _P, _P, _I64, _P, _I32, _I32, _P, _I32, _I64,
+                                         _I64, _P]),
+    "nf4_embedding_bnb_single": (ctypes.c_int, [_P, _I32, _I64, _P, _P, _I64, _I32, _P, _I32, _I64, _I64, _P]),
+    "nf4_embedding_bnb_cpu": (ctypes.c_int, [_P, _I32, _I64, _P, _P, _I64, _P, _P, _I64, _P, _I32, _I32, _P, _I32,
+                                             _I64, _I64, _I32]),
+    "nf4_embedding_bnb_single_cpu": (ctypes.c_int, [_P, _I32, _I64, _P, _P, _I64, _I32, _P, _I32, _I64, _I64, _I32]),
     "nf4_dequant_ref_cfg": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I32, _I64, _I64,
                                            ctypes.POINTER(LaunchCfg), _P]),
     "nf4_quant_workspace_bytes": (ctypes.c_size_t, [_I64, _I32]),

@@ -242,3 +242,63 @@ class Linear4bit(nn.Module):
         from .kernel import nf4_linear_bnb
 
         return nf4_linear_bnb(x, self, self.bias)
+
+
+class Embedding4bit(nn.Module):
+    """``bitsandbytes.nn.Embedding4bit`` / ``EmbeddingNF4`` stand-in: a token embedding whose
+    ``[num_embeddings, embedding_dim]`` table is NF4 storage (a ``Params4bit``).
+
+    ``forward(ids)`` gathers and dequantizes only the rows named (``kernel.nf4_embedding_bnb``:
+    one HIP launch, no host synchronisation, capturable in a graph); the table is never
+    dequantized as a whole.  The weight is frozen: no gradient, and ``padding_idx`` /
+    ``max_norm`` are not interpreted (a padding row returns what is stored).  ``as_linear()``
+    gives the tied ``lm_head`` over the same storage.
+    """
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, weight: Params4bit):
+        super().__init__()
+        self.num_embeddings = int(num_embeddings)
+        self.embedding_dim = int(embedding_dim)
+        self.weight = weight
+
+    @classmethod
+    def from_float(cls, embedding_or_weight, dtype=None, compress_statistics: bool = True, blocksize: int = 64):
+        """Build the module from an ``nn.Embedding`` or a ``[num_embeddings, embedding_dim]`` float
+        weight through the HIP quantizer (``quantize.nf4_quantize``) on the weight's device, as
+        ``Linear4bit.from_float`` does.  ``quant_state.dtype`` (the dtype ``forward`` returns) is
+        ``dtype`` if given, else the weight's."""
+        from .quantize import nf4_quantize
+
+        weight = embedding_or_weight.weight if isinstance(embedding_or_weight, nn.Module) else embedding_or_weight
+        if weight.dim() != 2:
+            raise ValueError(f"Embedding4bit.from_float: expected a [num_embeddings, embedding_dim] weight, got "
+                             f"{tuple(weight.shape)}")
+        rows, dim = int(weight.shape[0]), int(weight.shape[1])
+        packed, qs = nf4_quantize(weight, blocksize=blocksize, compress_statistics=compress_statistics)
+        if dtype is not None:
+            qs.dtype = dtype
+        qs.shape = torch.Size((rows, dim))
+        return cls(rows, dim, Params4bit(packed, qs))
+
+    def _apply(self, fn, recurse=True):
+        super()._apply(fn, recurse)
+        if self.weight.quant_state is not None:
+            self.weight.quant_state.to(self.weight.device)
+        return self
+
+    def forward(self, ids: torch.Tensor) -> torch.Tensor:
+        from .kernel import nf4_embedding_bnb
+
+        return nf4_embedding_bnb(ids, self)
+
+    def as_linear(self) -> "Linear4bit":
+        """The tied output projection: a bias-free ``Linear4bit`` with ``out_features =
+        num_embeddings`` and ``in_features = embedding_dim`` that holds this module's own
+        ``Params4bit`` object, so ``lm_head`` runs ``nf4_linear_bnb`` on the embedding's storage."""
+        lin = Linear4bit.__new__(Linear4bit)
+        nn.Module.__init__(lin)
+        lin.in_features, lin.out_features = self.embedding_dim, self.num_embeddings
+        lin.compute_dtype = self.weight.quant_state.dtype if self.weight.quant_state is not None else None
+        lin.weight = self.weight
+        lin.bias = None
+        return lin

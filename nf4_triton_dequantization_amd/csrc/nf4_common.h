@@ -74,6 +74,51 @@ __device__ __forceinline__ float nf4_code(uint32_t i) {
     return __uint_as_float(v);
 }
 
+// Scalar store of one output element (the per-byte / per-element kernels).
+template <int DT>
+__device__ __forceinline__ void store1(void* out, int64_t i, float x) {
+    if constexpr (DT == NF4DQ_BF16) {
+        reinterpret_cast<__bf16*>(out)[i] = (__bf16)x;
+    } else if constexpr (DT == NF4DQ_F16) {
+        reinterpret_cast<_Float16*>(out)[i] = (_Float16)opaque(x);
+    } else {
+        reinterpret_cast<float*>(out)[i] = x;
+    }
+}
+
+// Per-block table decode (16-bit outputs; the flat dequant kernel and the embedding gather).
+// The 8 lanes that share a 64-element block round its 16 possible outputs into a 32-byte
+// table at LDS byte `tb` (a multiple of 256, so byte 0 of tb is zero): lane k of the group
+// writes the outputs of codes 2k and 2k+1 as dword k.  An output is then the 16-bit entry at
+// tb + 2 * code, and 2 * code is a byte of (w >> 3) & 0x1E1E1E1E (high nibbles) or
+// (w << 1) & 0x1E1E1E1E (low nibbles): v_perm_b32 moves that byte into tb's byte 0, one
+// instruction per address.  A wave's LDS accesses complete in order, so the group needs no
+// barrier between its writes and its reads.
+typedef uint16_t __attribute__((may_alias)) u16_alias;  // table entries are written as dwords
+typedef uint32_t __attribute__((may_alias)) u32_alias;
+typedef uint32_t u32x4_alias __attribute__((ext_vector_type(4), may_alias));
+
+template <int DT>
+__device__ __forceinline__ void block_table_write(char* tbl, uint32_t tb, uint32_t k, f32x2 c01, float s) {
+    *reinterpret_cast<u32_alias*>(tbl + tb + 4u * k) = pack2<DT>(c01.x * s, c01.y * s);
+}
+
+// The 8 outputs of packed dword w (high nibble -> even element), two per output dword.
+__device__ __forceinline__ u32x4 block_table_decode(const char* tbl, uint32_t tb, uint32_t w) {
+    const uint32_t hb = (w >> 3) & 0x1E1E1E1Eu;
+    const uint32_t lb = (w << 1) & 0x1E1E1E1Eu;
+    uint32_t o[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const uint32_t ah = __builtin_amdgcn_perm(hb, tb, 0x03020104u + b);
+        const uint32_t al = __builtin_amdgcn_perm(lb, tb, 0x03020104u + b);
+        const uint32_t vh = *reinterpret_cast<const u16_alias*>(tbl + ah);
+        const uint32_t vl = *reinterpret_cast<const u16_alias*>(tbl + al);
+        o[b] = vh | (vl << 16);
+    }
+    return u32x4{o[0], o[1], o[2], o[3]};
+}
+
 // Buffer-resource flags word (raw buffer, dword format) for gfx950.
 constexpr int kRsrcFlags = 0x00020000;
 

@@ -77,18 +77,6 @@ using namespace nf4dq;
 #define NF4_FNOW() 0ull
 #endif
 
-// Scalar store of one output element (rows kernels).
-template <int DT>
-__device__ __forceinline__ void store1(void* out, int64_t i, float x) {
-    if constexpr (DT == NF4DQ_BF16) {
-        reinterpret_cast<__bf16*>(out)[i] = (__bf16)x;
-    } else if constexpr (DT == NF4DQ_F16) {
-        reinterpret_cast<_Float16*>(out)[i] = (_Float16)opaque(x);
-    } else {
-        reinterpret_cast<float*>(out)[i] = x;
-    }
-}
-
 // Variant hooks of the flat kernel: the product values by default.  tools/dq_variants.hip
 // redefines them to build A/B libraries (tools/_build/libnf4dq_dqv_<x>.so, timed in the
 // HBM-streamed regime by tools/stream_probe.py / cache_ab.py --libs); nothing in the
@@ -279,10 +267,8 @@ __device__ __forceinline__ void tile_finish(const Desc& D, __amdgpu_buffer_rsrc_
 // or (w << 1) & 0x1E1E1E1E (low nibbles): v_perm_b32 moves that byte into tb's byte 0,
 // one instruction per address.  The 8 lanes of a group write their table before any of
 // them reads it in program order, and a wave's LDS accesses complete in order, so no
-// barrier; the next dword's table reuses the region after this one's reads.
-typedef uint16_t __attribute__((may_alias)) u16_alias;  // table entries are written as dwords
-typedef uint32_t __attribute__((may_alias)) u32_alias;
-typedef uint32_t u32x4_alias __attribute__((ext_vector_type(4), may_alias));
+// barrier; the next dword's table reuses the region after this one's reads.  (The table
+// write and lookup themselves: block_table_write / block_table_decode, nf4_common.h.)
 
 struct TblCtx {
     char* tbl;    // LDS base of the workgroup's tables
@@ -308,20 +294,8 @@ __device__ __forceinline__ void tile_finish_tbl(const Desc& D, __amdgpu_buffer_r
     for (int j = 0; j < kU; ++j) {
         const uint32_t rel = 256u * j + 4u * lane;
         const float sj = __shfl(s, (int)(rel >> bsh), 64);
-        *reinterpret_cast<u32_alias*>(c.tbl + c.tb + 4u * k) = pack2<DT>(c.c01.x * sj, c.c01.y * sj);
-        const uint32_t w = in.w[j];
-        const uint32_t hb = (w >> 3) & 0x1E1E1E1Eu;
-        const uint32_t lb = (w << 1) & 0x1E1E1E1Eu;
-        uint32_t o[4];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const uint32_t ah = __builtin_amdgcn_perm(hb, c.tb, 0x03020104u + b);
-            const uint32_t al = __builtin_amdgcn_perm(lb, c.tb, 0x03020104u + b);
-            const uint32_t vh = *reinterpret_cast<const u16_alias*>(c.tbl + ah);
-            const uint32_t vl = *reinterpret_cast<const u16_alias*>(c.tbl + al);
-            o[b] = vh | (vl << 16);
-        }
-        const u32x4 ov = {o[0], o[1], o[2], o[3]};
+        block_table_write<DT>(c.tbl, c.tb, k, c.c01, sj);
+        const u32x4 ov = block_table_decode(c.tbl, c.tb, in.w[j]);
         __builtin_amdgcn_raw_buffer_store_b128(ov, ro, (base + rel) * 4u, 0, kAuxStore);
     }
 }

@@ -31,6 +31,7 @@
 #include <immintrin.h>
 
 #include "../../include/nf4_dequant.h"
+#include "nf4_embed_plan.h"
 #include "nf4_quant_plan.h"
 
 namespace {
@@ -421,6 +422,89 @@ int nf4_quant_bnb_nested_cpu(const void* w, int32_t in_dtype, int64_t numel, int
         }
     });
     return NF4DQ_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Host forms of the embedding gather (nf4_embed.hip): the validation is the device entries'
+// (nf4_embed_plan.h), the arithmetic the bitsandbytes-mode kernels' -- fp32 product of the
+// nested code and absmax2, then the offset added (two roundings), fp32 product with the NF4
+// code, one rounding to the output type -- so the same bits.  A plain loop over the output
+// rows, split over threads; an id outside [0, rows) gives a row of zero bits and reads
+// nothing from the table.
+// ---------------------------------------------------------------------------
+namespace {
+
+void embed_rows(const nf4dq::EmbedCall& c, float off, int64_t i0, int64_t i1) {
+    const int bsh = (int)nf4dq::embed_log2((uint64_t)c.blocksize);
+    const int bsh2 = c.single ? 0 : (int)nf4dq::embed_log2((uint64_t)c.blocksize2);
+    const size_t esize = c.out_dtype == NF4DQ_F32 ? 4 : 2;
+    for (int64_t i = i0; i < i1; ++i) {
+        bool ok;
+        int64_t id;
+        if (c.ids_dtype == NF4DQ_IDS_I64) {
+            id = reinterpret_cast<const int64_t*>(c.ids)[i];
+            ok = id >= 0 && id < c.rows;
+        } else {
+            const int32_t v = reinterpret_cast<const int32_t*>(c.ids)[i];
+            id = v;
+            ok = v >= 0 && (int64_t)v < c.rows;
+        }
+        char* row = reinterpret_cast<char*>(c.out) + (size_t)i * (size_t)c.dim * esize;
+        if (!ok) {
+            memset(row, 0, (size_t)c.dim * esize);
+            continue;
+        }
+        const int64_t e0 = id * c.dim;
+        for (int64_t j = 0; j < c.dim; ++j) {
+            const int64_t e = e0 + j;
+            const uint8_t byte = c.packed[e >> 1];
+            const int nib = (e & 1) ? (byte & 15) : (byte >> 4);
+            const int64_t b = e >> bsh;
+            float s;
+            if (c.single) {
+                s = c.a2[b];
+            } else {
+                const float p = c.code2[c.a1[b]] * c.a2[b >> bsh2];  // (-ffp-contract=off: rounded here)
+                s = p + off;
+            }
+            const float x = code_f(nib) * s;
+            if (c.out_dtype == NF4DQ_F32) reinterpret_cast<float*>(row)[j] = x;
+            else reinterpret_cast<uint16_t*>(row)[j] = c.out_dtype == NF4DQ_BF16 ? bf16_rne(x) : f16_rne(x);
+        }
+    }
+}
+
+int embed_cpu(const nf4dq::EmbedCall& c, int32_t threads) {
+    const nf4dq::EmbedPlan P = nf4dq::plan_embed(c);
+    if (P.rc != NF4DQ_OK || P.launches == 0) return P.rc;
+    const float off = (!c.single && c.offset) ? *c.offset : 0.0f;
+    // at least 64 Ki elements per worker
+    split_ranges(c.count, std::max<int64_t>(1, 65536 / c.dim), threads,
+                 [&c, off](int64_t i0, int64_t i1) { embed_rows(c, off, i0, i1); });
+    return NF4DQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nf4_embedding_bnb_cpu(const void* ids, int32_t ids_dtype, int64_t count, const uint8_t* packed,
+                          const uint8_t* absmax_q, int64_t nb, const float* code2, const float* absmax2, int64_t n2,
+                          const float* offset, int32_t blocksize, int32_t blocksize2, void* out, int32_t out_dtype,
+                          int64_t rows, int64_t dim, int32_t threads) {
+    const nf4dq::EmbedCall c{ids, ids_dtype, count, packed, absmax_q, nb, code2, absmax2, n2, offset,
+                             blocksize, blocksize2, out, out_dtype, rows, dim, false};
+    return embed_cpu(c, threads);
+}
+
+int nf4_embedding_bnb_single_cpu(const void* ids, int32_t ids_dtype, int64_t count, const uint8_t* packed,
+                                 const float* absmax, int64_t nabs, int32_t blocksize, void* out, int32_t out_dtype,
+                                 int64_t rows, int64_t dim, int32_t threads) {
+    const nf4dq::EmbedCall c{ids, ids_dtype, count, packed, nullptr, nabs, nullptr, absmax, 0, nullptr,
+                             blocksize, 0, out, out_dtype, rows, dim, true};
+    return embed_cpu(c, threads);
 }
 
 }  // extern "C"

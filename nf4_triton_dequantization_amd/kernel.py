@@ -396,6 +396,115 @@ def _launch_bnb(q, qs, out, code, numel, bs) -> int:
     return rc
 
 
+_IDS_CODE = {torch.int32: _lib.IDS_I32, torch.int64: _lib.IDS_I64}
+
+
+def _host_offset(off):
+    """``quant_state.offset`` for the host entries: (tensor kept alive, host pointer)."""
+    if off is None:
+        return None, None
+    if not torch.is_tensor(off):
+        off = torch.tensor(float(off), dtype=torch.float32)
+    off = off.to(device="cpu", dtype=torch.float32).contiguous()
+    if off.numel() != 1:
+        raise RuntimeError(f"nf4_embedding_bnb: quant_state.offset has {off.numel()} elements, expected 1")
+    return off, off.data_ptr()
+
+
+def nf4_embedding_bnb(ids: torch.Tensor, module, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Rows ``ids`` of an NF4 table in bitsandbytes semantics: ``dequantize_nf4_bnb(module)[ids]``
+    bit for bit, without dequantizing the table.
+
+    ``module.weight`` is a ``Params4bit`` whose ``quant_state.shape`` is ``[rows, dim]``;
+    ``ids`` has any shape, int32 or int64, on the weight's device.  Returns
+    ``ids.shape + (dim,)`` in ``quant_state.dtype`` (fp16, bf16 or fp32); ``out=`` takes a
+    contiguous tensor of that shape and dtype.  On a GPU weight this is ONE launch on the
+    current stream (``nf4_embedding_bnb`` / ``nf4_embedding_bnb_single``) that reads only the
+    selected rows' packed bytes and statistics and reads ``offset`` on the device: nothing is
+    read back, so the call can be captured in a graph.  An id outside ``[0, rows)`` gives a
+    row of zeros (never a device assert or an out-of-bounds read).  Host tensors run the
+    library's host path under ``NF4_BACKEND=cpu`` and raise otherwise.  There is no
+    fallback: a ``quant_type`` other than nf4, a blocksize that is not a power of two in
+    64..4096 (nested: a blocksize2 that is not a power of two >= 4), an ``ids`` dtype other
+    than int32 / int64 or ``ids`` on another device raise.
+    """
+    weight = module.weight
+    qs = weight.quant_state
+    qweight = weight.data
+    dev = qweight.device
+    on_host = dev.type != "cuda"
+    if on_host and (dev.type != "cpu" or backend() != "cpu"):
+        _require_device(qweight)
+    qt = getattr(qs, "quant_type", None)
+    if qt != "nf4":
+        raise ValueError(f"nf4_embedding_bnb: quant_type {qt!r} is not supported, expected 'nf4'")
+    shape = tuple(int(s) for s in qs.shape) if getattr(qs, "shape", None) is not None else ()
+    if len(shape) != 2:
+        raise ValueError(f"nf4_embedding_bnb: quant_state.shape {shape} is not [rows, dim]")
+    rows, dim = shape
+    bs = int(qs.blocksize)
+    if bs < 64 or bs > 4096 or bs & (bs - 1):
+        raise ValueError(f"nf4_embedding_bnb: blocksize {bs} is not a power of two in 64..4096")
+    nested = getattr(qs, "state2", None) is not None and qs.absmax.dtype == torch.uint8  # as _launch_bnb
+    bs2 = int(qs.state2.blocksize) if nested else 0
+    if nested and (bs2 < 4 or bs2 & (bs2 - 1)):
+        raise ValueError(f"nf4_embedding_bnb: state2.blocksize {bs2} is not a power of two >= 4")
+    if not torch.is_tensor(ids) or ids.dtype not in _IDS_CODE:
+        raise TypeError(f"nf4_embedding_bnb: ids dtype {getattr(ids, 'dtype', type(ids))} is not supported, "
+                        f"expected torch.int32 or torch.int64")
+    if ids.device != dev:
+        raise RuntimeError(f"nf4_embedding_bnb: ids on '{ids.device}', weight on '{dev}': both must be on the "
+                           f"same device")
+    code = _dtype_code(qs.dtype)
+    if qweight.dtype != torch.uint8:
+        raise TypeError(f"nf4_embedding_bnb: packed weight dtype {qweight.dtype} is not supported, expected "
+                        f"torch.uint8")
+    if qweight.numel() < (rows * dim + 1) // 2:
+        raise RuntimeError(f"nf4_embedding_bnb: packed weight has {qweight.numel()} bytes, [{rows}, {dim}] "
+                           f"needs {(rows * dim + 1) // 2}")
+    want = tuple(ids.shape) + (dim,)
+    if out is None:
+        out = torch.empty(want, dtype=qs.dtype, device=dev)
+    elif (tuple(out.shape) != want or out.dtype != qs.dtype or out.device != dev or not out.is_contiguous()):
+        raise ValueError(f"nf4_embedding_bnb: out must be a contiguous {qs.dtype} tensor of shape {want} on "
+                         f"'{dev}', got {out.dtype} {tuple(out.shape)} on '{out.device}'")
+    count = ids.numel()
+    if count == 0 or dim == 0:
+        return out
+    idc = ids.contiguous()
+    q, qp, _ = _flat_ptr(qweight)
+    L = _lib.lib()
+    head = (idc.data_ptr(), _IDS_CODE[idc.dtype], count, qp)
+    if nested:
+        _on_device(dev, qs.absmax, qs.state2.code, qs.state2.absmax)
+        a1, ap, an = _flat_ptr(qs.absmax)
+        c2 = qs.state2.code
+        c2, cp, cn = _flat_ptr(c2 if c2.dtype == torch.float32 else c2.to(torch.float32))
+        a2 = qs.state2.absmax
+        a2, bp, bn = _flat_ptr(a2 if a2.dtype == torch.float32 else a2.to(torch.float32))
+        if cn != 256:
+            raise RuntimeError(f"nf4_embedding_bnb: state2.code has {cn} entries, expected 256")
+        off, op = _host_offset(qs.offset) if on_host else _offset_ptr(qs.offset, dev)
+        args = head + (ap, an, cp, bp, bn, op, bs, bs2, out.data_ptr(), code, rows, dim)
+        if on_host:
+            rc = L.nf4_embedding_bnb_cpu(*args, cpu_threads())
+        else:
+            with torch.cuda.device(dev):  # the launch's device = the weight's (not the current one)
+                rc = L.nf4_embedding_bnb(*args, _raw_stream(dev.index))
+    else:
+        _on_device(dev, qs.absmax)
+        am = qs.absmax
+        am, ap, an = _flat_ptr(am if am.dtype == torch.float32 else am.to(torch.float32))
+        args = head + (ap, an, bs, out.data_ptr(), code, rows, dim)
+        if on_host:
+            rc = L.nf4_embedding_bnb_single_cpu(*args, cpu_threads())
+        else:
+            with torch.cuda.device(dev):
+                rc = L.nf4_embedding_bnb_single(*args, _raw_stream(dev.index))
+    _lib.check(rc, "nf4 embedding")
+    return out
+
+
 # (device index, raw stream handle) -> (workspace, the torch stream object): holding the
 # stream object keeps a torch-created stream alive for the cache's lifetime, so the
 # check below never hands HIP a dangling handle (an ExternalStream's owner must keep
