@@ -423,6 +423,49 @@ int nf4_gemm_bnb_grouped(const void* x, int64_t M, int64_t K, const void* mats, 
                          int32_t single, int32_t out_dtype, void* workspace, size_t workspace_bytes,
                          const nf4_gemm_cfg* cfg, void* hip_stream);
 
+/* The fused GEMM in bitsandbytes semantics for 33..128 rows (batched decode, a speculative
+ * verify step, a short prompt): the row-tiled kernel family.  The values are nf4_gemm_bnb's /
+ * nf4_gemm_bnb_single's: W bit for bit what nf4_dequant_bnb / nf4_dequant_bnb_single write (two
+ * fp32 products and one RNE per weight, never a fused multiply-add; `offset` ONE fp32 ON THE
+ * DEVICE, NULL = 0), fp32 accumulation on MFMA, one final rounding to out_dtype (fp16 / bf16).
+ * Every weight is decoded once per workgroup and multiplied with all row tiles; x is staged
+ * through LDS in 128-deep chunks.
+ * Shapes: 1 <= M <= NF4DQ_GEMM_MT_MAX_M (the whole range, so that tile edges can be tested;
+ * below 33 rows nf4_gemm_bnb is the faster entry), N % 64 == 0 and N >= 64, K % 128 == 0 and
+ * K >= 128, packed_len == N*K/2, blocksize == 64 (a larger valid blocksize: NF4DQ_ERR_SHAPE),
+ * nb / nabs >= N*K/64 and n2 >= ceil(that / blocksize2); else NF4DQ_ERR_SHAPE -- M == 0 and
+ * N == 0 included.  N > 2^18: NF4DQ_ERR_TOO_LARGE.  A null pointer (offset excepted), x / packed
+ * not 16-byte or y not 8-byte aligned, a bad dtype or a block size that is no power of two:
+ * NF4DQ_ERR_ARG.
+ * cfg NULL = the library's choice.  A cfg names kernel NF4DQ_GEMM_MT (0 = the same) with
+ *   waves   waves per workgroup, 2 / 4: a workgroup owns 32 * waves columns (N must divide)
+ *   depth   K stage in 128-deep chunks: 1
+ *   ksplit  K slices, 1 .. min(K / 128, 16); ceil(K/128 / ksplit) chunks per slice, so the
+ *           last slices may be short or empty
+ *   strips  16-column strips per wave: 2 (0 = 2)
+ * and never falls back: an invalid one is NF4DQ_ERR_ARG.  The row-tile count follows from M.
+ * Workspace (nf4_gemm_bnb_mt_workspace_bytes; 0 = none, one K slice): nf4_gemm_ref's layout
+ * and contract -- 16-byte aligned, zero-filled before its first use, left zero by every call,
+ * one per stream, shareable with the other fused entries.  K slices write fp32 partials to a
+ * slab, make them visible (agent-scope release) and draw a ticket; the slice drawing the last
+ * ticket acquires, sums all slices in slice order, stores y and clears the slab and the
+ * ticket.  No workgroup waits for another, so this family cannot time out and never sets the
+ * split-K error word; the result is a function of the inputs and the cfg alone.
+ * Asynchronous on `hip_stream`; one launch; allocates nothing; capturable in a graph. */
+#define NF4DQ_GEMM_MT_MAX_M 128
+#define NF4DQ_GEMM_MT 8
+size_t nf4_gemm_bnb_mt_workspace_bytes(int64_t M, int64_t N, int64_t K, const nf4_gemm_cfg* cfg);
+int nf4_gemm_bnb_mt(const void* x, int64_t M, const uint8_t* packed, int64_t packed_len,
+                    const uint8_t* absmax_q, int64_t nb, const float* code2,
+                    const float* absmax2, int64_t n2, const float* offset,
+                    int32_t blocksize, int32_t blocksize2,
+                    void* y, int32_t out_dtype, int64_t N, int64_t K,
+                    void* workspace, size_t workspace_bytes, const nf4_gemm_cfg* cfg, void* hip_stream);
+int nf4_gemm_bnb_mt_single(const void* x, int64_t M, const uint8_t* packed, int64_t packed_len,
+                           const float* absmax, int64_t nabs, int32_t blocksize,
+                           void* y, int32_t out_dtype, int64_t N, int64_t K,
+                           void* workspace, size_t workspace_bytes, const nf4_gemm_cfg* cfg, void* hip_stream);
+
 /* The split-K hand-off never hangs: a reducer that has polled a partner slice's
  * entries 2^16 times without seeing them gives up, reads them as NaN and sets a
  * sticky error word in the workspace header.  This call waits for `hip_stream`,

@@ -36,6 +36,7 @@ BATCH_MAX = 24
 IDS_I32 = 0
 IDS_I64 = 1
 GEMM_MAX_M = 32
+GEMM_MT_MAX_M = 128  # NF4DQ_GEMM_MT_MAX_M: rows of the row-tiled entries (nf4_gemm_bnb_mt*)
 
 
 class MatrixDesc(ctypes.Structure):
@@ -76,6 +77,7 @@ GEMM_XS = 4
 GEMM_XR = 5
 GEMM_SK = 6  # retired in round 6: rejected with ERR_ARG
 GEMM_GEMV = 7  # the decode GEMV (M = 1, K % 2048 == 0)
+GEMM_MT = 8  # the row-tiled family (nf4_gemm_bnb_mt*: up to 128 rows); its own entries only
 
 
 GEMM_GROUP_MAX = 8
@@ -147,6 +149,11 @@ SIGNATURES = {
     "nf4_gemm_bnb_grouped_workspace_bytes": (ctypes.c_size_t, [_I64, _I64, _P, _I32, _I32, ctypes.POINTER(GemmCfg)]),
     "nf4_gemm_bnb_grouped": (ctypes.c_int, [_P, _I64, _I64, _P, _I32, _I32, _I32, _P, ctypes.c_size_t,
                                             ctypes.POINTER(GemmCfg), _P]),
+    "nf4_gemm_bnb_mt_workspace_bytes": (ctypes.c_size_t, [_I64, _I64, _I64, ctypes.POINTER(GemmCfg)]),
+    "nf4_gemm_bnb_mt": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _P, _I32, _I32, _P, _I32, _I64, _I64,
+                                       _P, ctypes.c_size_t, ctypes.POINTER(GemmCfg), _P]),
+    "nf4_gemm_bnb_mt_single": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _I32, _P, _I32, _I64, _I64, _P,
+                                              ctypes.c_size_t, ctypes.POINTER(GemmCfg), _P]),
     "nf4_gemm_check_workspace": (ctypes.c_int, [_P, ctypes.c_size_t, _P]),
     "nf4_strerror": (ctypes.c_char_p, [ctypes.c_int]),
     "nf4_version": (ctypes.c_char_p, []),

@@ -641,6 +641,16 @@ def _offset_ptr(off, device):
     return off, off.data_ptr()
 
 
+# Rows up to which nf4_linear_bnb routes to the row-tiled entry (nf4_gemm_bnb_mt*): the largest
+# M of {64, 96, 128} at which it measured faster than both dequantize + matmul and ceil(M / 32)
+# nf4_gemm_bnb calls on row slices at 4096^2, 14336x4096 and 4096x14336 by more than the
+# run-to-run spread (profiles/gemm_mt/).  That holds at 128 rows (narrowly at
+# 4096^2: 34.6 against 35.4 us for the slices, spread 0.3 %).  Below it the entry beats the
+# composite -- the only other route this function has -- at every measured M and shape, but at
+# 64 and 96 rows the row slices, a C-ABI route, are faster where K = 4096.
+GEMM_MT_ROUTED_M = 128
+
+
 def _bnb_gemm_blocksizes(qs) -> bool:
     """The statistics block sizes the fused bnb GEMM takes: blocksize a power of two in
     64..4096 and, when nested, blocksize2 a power of two >= 4 (others dequantize + matmul)."""
@@ -665,8 +675,13 @@ def nf4_linear_bnb(x: torch.Tensor, module, bias: Optional[torch.Tensor] = None)
     fused path is taken when the weight is on a GPU, ``quant_state.dtype`` is fp16 or bf16,
     0 < M <= ``GEMM_MAX_M`` rows, N % 64 == 0, K % 128 == 0, the packed weight is uint8 of
     N * K / 2 bytes, ``quant_type`` is nf4 and no gradient is being recorded for ``x`` (the
-    fused call is not differentiable).  Everything else dequantizes with the HIP kernel and
-    multiplies with torch, which autograd follows.  Both paths use the same weights and fp32
+    fused call is not differentiable).  ``GEMM_MAX_M`` < M <= ``GEMM_MT_ROUTED_M`` rows
+    (batched decode, a speculative verify step, a short prompt) take the row-tiled entry
+    (``nf4_gemm_bnb_mt`` / ``nf4_gemm_bnb_mt_single``) under the same rules when ``blocksize``
+    is 64: again one launch, no host read of the offset, capturable.  Everything else --
+    a gradient being recorded for ``x``, other block sizes above ``GEMM_MAX_M`` rows, CPU
+    tensors, more rows than ``GEMM_MT_ROUTED_M`` -- dequantizes with the HIP kernel and
+    multiplies with torch, which autograd follows.  All paths use the same weights and fp32
     accumulation; the summation order differs, so the last bit of ``y`` may.
     """
     weight = module.weight
@@ -681,10 +696,14 @@ def nf4_linear_bnb(x: torch.Tensor, module, bias: Optional[torch.Tensor] = None)
     lead = x.shape[:-1]
     M = x.numel() // K if K else 0
     fused = (qweight.device.type == "cuda" and dtype in (torch.float16, torch.bfloat16)
-             and 0 < M <= _lib.GEMM_MAX_M and N % 64 == 0 and K % 128 == 0
+             and 0 < M <= GEMM_MT_ROUTED_M and N % 64 == 0 and K % 128 == 0
              and qweight.dtype == torch.uint8 and qweight.numel() == N * K // 2
              and getattr(qs, "quant_type", None) == "nf4" and _bnb_gemm_blocksizes(qs)
              and not (torch.is_grad_enabled() and x.requires_grad))
+    # above GEMM_MAX_M rows: the row-tiled entry, which takes blocksize 64 alone
+    mt = fused and M > _lib.GEMM_MAX_M
+    if mt and not (int(qs.blocksize) == 64 and N >= 64 and K >= 128 and qweight.data_ptr() % 16 == 0):
+        fused = False  # (the entry loads 16 bytes at a time: a weight view at an odd offset dequantizes)
     if not fused:
         w = dequantize_nf4_bnb(module)
         y = x.to(w.dtype) @ w.t()
@@ -694,16 +713,20 @@ def nf4_linear_bnb(x: torch.Tensor, module, bias: Optional[torch.Tensor] = None)
         if xc.dtype != dtype:
             xc = xc.to(dtype)
         xc = xc.contiguous()
+        if mt and xc.data_ptr() % 16:
+            xc = xc.clone()  # a view at an odd offset: the row-tiled entry loads 16 bytes at a time
         y = torch.empty((M, N), dtype=dtype, device=dev)
         L = _lib.lib()
         bs = int(qs.blocksize)
         nested = getattr(qs, "state2", None) is not None and qs.absmax.dtype == torch.uint8  # as _launch_bnb
         with torch.cuda.device(dev):
-            ws_bytes = L.nf4_gemm_bnb_workspace_bytes(M, N, K, None)
+            ws_bytes = (L.nf4_gemm_bnb_mt_workspace_bytes if mt else L.nf4_gemm_bnb_workspace_bytes)(M, N, K, None)
             ws = _gemm_workspace(dev, ws_bytes) if ws_bytes else None
             wp = ws.data_ptr() if ws is not None else None
             q, qp, qn = _flat_ptr(qweight)
             stream = torch.cuda.current_stream().cuda_stream
+            gemm_nested = L.nf4_gemm_bnb_mt if mt else L.nf4_gemm_bnb
+            gemm_single = L.nf4_gemm_bnb_mt_single if mt else L.nf4_gemm_bnb_single
             if nested:
                 _on_device(dev, qs.absmax, qs.state2.code, qs.state2.absmax)
                 a1, ap, an = _flat_ptr(qs.absmax)
@@ -714,14 +737,14 @@ def nf4_linear_bnb(x: torch.Tensor, module, bias: Optional[torch.Tensor] = None)
                 if cn != 256:
                     raise RuntimeError(f"nf4_linear_bnb: state2.code has {cn} entries, expected 256")
                 off, op = _offset_ptr(qs.offset, dev)
-                rc = L.nf4_gemm_bnb(xc.data_ptr(), M, qp, qn, ap, an, cp, bp, bn, op, bs, int(qs.state2.blocksize),
-                                    y.data_ptr(), _dtype_code(dtype), N, K, wp, ws_bytes, None, stream)
+                rc = gemm_nested(xc.data_ptr(), M, qp, qn, ap, an, cp, bp, bn, op, bs, int(qs.state2.blocksize),
+                                 y.data_ptr(), _dtype_code(dtype), N, K, wp, ws_bytes, None, stream)
             else:
                 _on_device(dev, qs.absmax)
                 am = qs.absmax
                 am, ap, an = _flat_ptr(am if am.dtype == torch.float32 else am.to(torch.float32))
-                rc = L.nf4_gemm_bnb_single(xc.data_ptr(), M, qp, qn, ap, an, bs, y.data_ptr(), _dtype_code(dtype),
-                                           N, K, wp, ws_bytes, None, stream)
+                rc = gemm_single(xc.data_ptr(), M, qp, qn, ap, an, bs, y.data_ptr(), _dtype_code(dtype),
+                                 N, K, wp, ws_bytes, None, stream)
         _lib.check(rc, "nf4 fused bnb gemm")
         y = y.reshape(*lead, N)
     if bias is not None:

@@ -25,6 +25,12 @@ rotation of distinct weights larger than the Infinity Cache, and then the whole 
   forward    Linear4bit.forward (nf4_linear_bnb: one fused launch), eager, wall clock
   unfused    what forward did before: dequantize_nf4_bnb (host read of the offset) + matmul,
              eager, wall clock
+  (``--ms 48,64,96,128``: rows above NF4DQ_GEMM_MAX_M.  Per shape and M three graphs of >= 100
+   calls each over the rotation, replayed in turn for ``rounds`` rounds and timed with device
+   events: mt = nf4_gemm_bnb_mt; composite = nf4_dequant_bnb into a 16-bit temporary +
+   torch.matmul, the path it replaces in nf4_linear_bnb, here without that path's host read of
+   the offset; sliced = ceil(M / 32) calls of nf4_gemm_bnb on row slices.  Also the composite
+   eager with the host read, wall clock, and the achieved bytes/s from the algorithmic bytes.)
   grouped    (the pass only) nf4_gemm_bnb_grouped: q/k/v in one launch, gate/up in one, o and
              down through nf4_gemm_bnb -- 128 launches -- replayed in turn with the per-weight
              bnb pass (224 launches, from ``--parent-lib`` when given: another build of the
@@ -278,15 +284,90 @@ def main_bnb(args):
                           "faster_by_more_than_the_spread": bool(min(gain) > self_spread),
                           "grouped_over_ref_grouped": round(med(gr) / med(rg), 4)}), flush=True)
 
+    def measure_mt(label, mods, M):
+        """33..128 rows: the row-tiled entry (nf4_gemm_bnb_mt) against the composite it replaces
+        in nf4_linear_bnb and against ceil(M / 32) calls of nf4_gemm_bnb on row slices."""
+        n, k = mods[0].out_features, mods[0].in_features
+        calls = -(-max(100, len(mods)) // len(mods)) * len(mods)  # >= 100, whole turns of the rotation
+        x = torch.randn((M, k), device=dev, generator=gen).to(torch.bfloat16)
+        y = torch.empty((M, n), dtype=torch.bfloat16, device=dev)
+        wtmp = torch.empty((n, k), dtype=torch.bfloat16, device=dev)  # the composite's 16-bit temporary
+        slices = [(r, min(32, M - r)) for r in range(0, M, 32)]
+        wsz = max(L.nf4_gemm_bnb_mt_workspace_bytes(M, n, k, None), L.nf4_gemm_bnb_workspace_bytes(32, n, k, None),
+                  L.nf4_gemm_bnb_workspace_bytes(slices[-1][1], n, k, None))
+        work = torch.zeros(max(wsz, 1 << 16), dtype=torch.uint8, device=dev)
+        t = []
+        for m in mods:
+            qs = m.weight.quant_state
+            t.append((m.weight.data, qs.absmax, qs.state2.code, qs.state2.absmax, qs.offset, float(qs.offset)))
+
+        def mt():
+            sp = torch.cuda.current_stream().cuda_stream
+            for i in range(calls):
+                q, a1, c2, a2, off, _ = t[i % len(t)]
+                rc = L.nf4_gemm_bnb_mt(x.data_ptr(), M, q.data_ptr(), q.numel(), a1.data_ptr(), a1.numel(), c2.data_ptr(),
+                                       a2.data_ptr(), a2.numel(), off.data_ptr(), 64, 256, y.data_ptr(), _lib.BF16, n, k,
+                                       work.data_ptr(), wsz, None, sp)
+                assert rc == 0, rc
+
+        def composite():  # nf4_linear_bnb's other path, without its host read of the offset
+            import ctypes
+
+            sp = torch.cuda.current_stream().cuda_stream
+            for i in range(calls):
+                q, a1, c2, a2, _, off = t[i % len(t)]
+                rc = L.nf4_dequant_bnb(q.data_ptr(), a1.data_ptr(), a1.numel(), c2.data_ptr(), a2.data_ptr(), a2.numel(),
+                                       ctypes.c_float(off), wtmp.data_ptr(), _lib.BF16, n * k, 64, 256, sp)
+                assert rc == 0, rc
+                torch.matmul(x, wtmp.t(), out=y)
+
+        def sliced():
+            sp = torch.cuda.current_stream().cuda_stream
+            for i in range(calls):
+                q, a1, c2, a2, off, _ = t[i % len(t)]
+                for r, rows in slices:
+                    rc = L.nf4_gemm_bnb(x.data_ptr() + r * k * 2, rows, q.data_ptr(), q.numel(), a1.data_ptr(), a1.numel(),
+                                        c2.data_ptr(), a2.data_ptr(), a2.numel(), off.data_ptr(), 64, 256,
+                                        y.data_ptr() + r * n * 2, _lib.BF16, n, k, work.data_ptr(), wsz, None, sp)
+                    assert rc == 0, rc
+
+        def eager(i):  # exactly what nf4_linear_bnb ran for these M before: host read of the offset included
+            w = dequantize_nf4_bnb(mods[i % len(mods)])
+            x @ w.t()
+
+        with torch.no_grad():
+            tm, tc, ts = _interleaved_rounds((mt, composite, sliced), calls, args.rounds)
+            eager(0)
+            te = _wall_us(eager, calls)
+        assert L.nf4_gemm_check_workspace(work.data_ptr(), wsz, torch.cuda.current_stream().cuda_stream) == 0
+        assert int(work.count_nonzero()) == 0
+        med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+        nblk = n * k // 64
+        algo = n * k // 2 + nblk + -(-nblk // 256) * 4 + M * k * 2 + M * n * 2
+        print(json.dumps({"semantics": "bnb", "what": label, "M": M, "calls": calls, "distinct_weights": len(mods),
+                          "packed_mib_per_round": round(calls * n * k / 2 / 2 ** 20, 1),
+                          "mt_us": [round(v, 3) for v in tm], "composite_us": [round(v, 3) for v in tc],
+                          "sliced_us": [round(v, 3) for v in ts], "mt_med": round(med(tm), 3),
+                          "composite_med": round(med(tc), 3), "sliced_med": round(med(ts), 3),
+                          "composite_eager_wall_us": round(te, 3),
+                          "composite_over_mt_min": round(min(c / m for c, m in zip(tc, tm)), 4),
+                          "sliced_over_mt_min": round(min(c / m for c, m in zip(ts, tm)), 4),
+                          "algorithmic_bytes": algo, "mt_tb_per_s": round(algo / med(tm) / 1e6, 3),
+                          "share_of_8tb_per_s": round(algo / med(tm) / 1e6 / (PEAK / 1e12), 4)}), flush=True)
+
     ms = [int(v) for v in args.ms.split(",")]
     for sh in [s for s in args.shapes.split(";") if s]:
         n, k = (int(v) for v in sh.split(","))
         copies = max(8, args.budget_mb * (1 << 20) // (n * k // 2))
         mods = [quantized(n, k) for _ in range(copies)]
         for M in ms:
-            measure(f"{n}x{k}", mods, M)
+            if M > _lib.GEMM_MAX_M:  # 33..128 rows: the row-tiled entry and its alternatives
+                measure_mt(f"{n}x{k}", mods, M)
+            else:
+                measure(f"{n}x{k}", mods, M)
         del mods
-    if args.layers > 0:
+    ms = [M for M in ms if M <= _lib.GEMM_MAX_M]  # the whole pass: decode sizes only
+    if args.layers > 0 and ms:
         mods = [quantized(n, k) for _ in range(args.layers) for (n, k) in SHAPES]
         for M in ms:
             if not args.grouped_only:
