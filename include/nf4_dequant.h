@@ -466,6 +466,67 @@ int nf4_gemm_bnb_mt_single(const void* x, int64_t M, const uint8_t* packed, int6
                            void* y, int32_t out_dtype, int64_t N, int64_t K,
                            void* workspace, size_t workspace_bytes, const nf4_gemm_cfg* cfg, void* hip_stream);
 
+/* The fused expert GEMM of a mixture-of-experts block in bitsandbytes semantics: ONE launch
+ * per projection for all experts, routed on the device.  With `experts` weights of one shape
+ * [N][K], P (token, choice) pairs and int32 expert_ids[P] ON THE DEVICE,
+ *   y[p][:] = x[p / x_div][:] . W_{expert_ids[p]}^T          for p in 0 .. P-1
+ * with W_e bit for bit what nf4_dequant_bnb / nf4_dequant_bnb_single write for expert e (nested:
+ * fl32(fl32(code2_e[absmax_q] * absmax2) + offset_e), then the code times that scale with one
+ * RNE to 16 bits, never a fused multiply-add), fp32 accumulation on MFMA and one final rounding
+ * to out_dtype (fp16 / bf16).  x_div = how many consecutive pairs share one row of x: top_k for
+ * a projection of the token's hidden state (x has ceil(P / x_div) rows; nothing past them is
+ * read), 1 for one of per-pair activations.  A pair whose id is outside [0, experts) gets a row
+ * of zeros, as nf4_embedding_bnb treats an id outside the table; one token may name the same
+ * expert twice.  Every row of y ([P][N], dense) is stored by the launch; nothing else is
+ * written but the workspace.  The ids are read when the kernel runs: no host copy, no
+ * synchronisation, and a captured graph follows the router from replay to replay.  An expert
+ * without a pair costs no weight or statistics traffic.
+ * The experts are stacked: one base pointer per kind of data and a stride between experts
+ * (`experts` points at ONE nf4_moe_experts in host memory; it is `const void*`, as `expert_ids`
+ * is, so that every prototype of this header keeps to the plain parameter types bindings are
+ * derived from).  Every expert has its own statistics, its own offset and, with code2_stride
+ * != 0, its own code2 table.
+ * Rules (nf4_gemm_bnb_mt's, with its codes): 1 <= P <= NF4DQ_MOE_MAX_PAIRS, N % 64 == 0 and
+ * N >= 64, K % 128 == 0 and K >= 128, blocksize == 64 (a larger valid one: NF4DQ_ERR_SHAPE),
+ * packed_stride >= N*K/2, nb_stride >= N*K/64, n2_stride >= ceil(N*K/64 / blocksize2) (single:
+ * >= N*K/64), code2_stride 0 or >= 256; else NF4DQ_ERR_SHAPE.  N > 2^18, more split-K tickets
+ * (experts * column tiles) than the workspace header holds: NF4DQ_ERR_TOO_LARGE.  A null
+ * pointer (offset excepted), x / packed not 16-byte, y not 8-byte or expert_ids not 4-byte
+ * aligned, packed_stride % 16 != 0, a bad dtype, a block size that is no power of two,
+ * experts outside 1 .. NF4DQ_MOE_MAX_EXPERTS, x_div < 1 or a negative size: NF4DQ_ERR_ARG.
+ * P == 0: NF4DQ_OK, nothing launched.
+ * cfg NULL = the library's choice from (P, experts, N, K, CU count) alone.  A cfg names kernel
+ * NF4DQ_GEMM_MOE (0 = the same) with nf4_gemm_bnb_mt's fields (waves 2 / 4, depth 1, ksplit
+ * 1 .. min(K / 128, 16), strips 2 or 0) and never falls back: an invalid one is NF4DQ_ERR_ARG.
+ * Workspace (nf4_gemm_bnb_moe_workspace_bytes; 0 = none, one K slice): nf4_gemm_ref's layout and
+ * contract -- the ticket header, then ksplit slabs of P * N floats indexed by pair, all zero
+ * between calls, shareable with the other fused entries.  One ticket per (expert, column
+ * tile); no workgroup waits for another, so the split-K error word is never set, and the result
+ * is a function of the inputs and the cfg alone.
+ * Asynchronous on `hip_stream`; one launch; allocates nothing; capturable in a graph. */
+#define NF4DQ_MOE_MAX_PAIRS 128
+#define NF4DQ_MOE_MAX_EXPERTS 256
+#define NF4DQ_GEMM_MOE 9
+typedef struct nf4_moe_experts {
+    const uint8_t* packed;   /* expert e: packed + e * packed_stride, N*K/2 bytes */
+    int64_t packed_stride;   /* bytes between experts, >= N*K/2, % 16 == 0 */
+    const uint8_t* absmax_q; /* nested; NULL in single mode */
+    int64_t nb_stride;       /* bytes between experts; 0 in single mode */
+    const float* code2;      /* nested: 256 fp32 on the device per table; NULL in single mode */
+    int64_t code2_stride;    /* floats: 0 = one table shared by all experts, else >= 256 */
+    const float* absmax2;    /* nested: absmax2; single: the fp32 absmax */
+    int64_t n2_stride;       /* floats between experts */
+    const float* offset;     /* nested: `experts` fp32 ON THE DEVICE, or NULL (= 0) */
+    int64_t N, K;            /* every expert's shape */
+    int32_t experts;         /* 1 .. NF4DQ_MOE_MAX_EXPERTS */
+    int32_t single;          /* 0: nested statistics; != 0: fp32 absmax */
+    int32_t blocksize, blocksize2; /* blocksize2 ignored in single mode */
+} nf4_moe_experts;
+size_t nf4_gemm_bnb_moe_workspace_bytes(int64_t P, const void* experts, const nf4_gemm_cfg* cfg);
+int nf4_gemm_bnb_moe(const void* x, const void* expert_ids, int64_t P, int32_t x_div, const void* experts,
+                     void* y, int32_t out_dtype, void* workspace, size_t workspace_bytes,
+                     const nf4_gemm_cfg* cfg, void* hip_stream);
+
 /* The split-K hand-off never hangs: a reducer that has polled a partner slice's
  * entries 2^16 times without seeing them gives up, reads them as NaN and sets a
  * sticky error word in the workspace header.  This call waits for `hip_stream`,

@@ -78,6 +78,9 @@ GEMM_XR = 5
 GEMM_SK = 6  # retired in round 6: rejected with ERR_ARG
 GEMM_GEMV = 7  # the decode GEMV (M = 1, K % 2048 == 0)
 GEMM_MT = 8  # the row-tiled family (nf4_gemm_bnb_mt*: up to 128 rows); its own entries only
+GEMM_MOE = 9  # the expert GEMM of a mixture-of-experts block (nf4_gemm_bnb_moe); its own entry only
+MOE_MAX_PAIRS = 128    # NF4DQ_MOE_MAX_PAIRS: (token, choice) pairs of one nf4_gemm_bnb_moe launch
+MOE_MAX_EXPERTS = 256  # NF4DQ_MOE_MAX_EXPERTS
 
 
 GEMM_GROUP_MAX = 8
@@ -98,6 +101,16 @@ class GemmBnbMat(ctypes.Structure):
                 ("nb", ctypes.c_int64), ("code2", ctypes.c_void_p), ("absmax2", ctypes.c_void_p),
                 ("n2", ctypes.c_int64), ("offset", ctypes.c_void_p), ("blocksize", ctypes.c_int32),
                 ("blocksize2", ctypes.c_int32), ("y", ctypes.c_void_p), ("N", ctypes.c_int64)]
+
+
+class MoeExperts(ctypes.Structure):
+    """nf4_moe_experts (include/nf4_dequant.h): the stacked experts of nf4_gemm_bnb_moe."""
+
+    _fields_ = [("packed", ctypes.c_void_p), ("packed_stride", ctypes.c_int64), ("absmax_q", ctypes.c_void_p),
+                ("nb_stride", ctypes.c_int64), ("code2", ctypes.c_void_p), ("code2_stride", ctypes.c_int64),
+                ("absmax2", ctypes.c_void_p), ("n2_stride", ctypes.c_int64), ("offset", ctypes.c_void_p),
+                ("N", ctypes.c_int64), ("K", ctypes.c_int64), ("experts", ctypes.c_int32), ("single", ctypes.c_int32),
+                ("blocksize", ctypes.c_int32), ("blocksize2", ctypes.c_int32)]
 
 
 class GemmCfg(ctypes.Structure):
@@ -154,6 +167,10 @@ SIGNATURES = {
                                        _P, ctypes.c_size_t, ctypes.POINTER(GemmCfg), _P]),
     "nf4_gemm_bnb_mt_single": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _I32, _P, _I32, _I64, _I64, _P,
                                               ctypes.c_size_t, ctypes.POINTER(GemmCfg), _P]),
+    # `experts`: const void* in the header, pointing at ONE MoeExperts; `expert_ids`: int32 on the device
+    "nf4_gemm_bnb_moe_workspace_bytes": (ctypes.c_size_t, [_I64, _P, ctypes.POINTER(GemmCfg)]),
+    "nf4_gemm_bnb_moe": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _I32, _P, ctypes.c_size_t,
+                                        ctypes.POINTER(GemmCfg), _P]),
     "nf4_gemm_check_workspace": (ctypes.c_int, [_P, ctypes.c_size_t, _P]),
     "nf4_strerror": (ctypes.c_char_p, [ctypes.c_int]),
     "nf4_version": (ctypes.c_char_p, []),

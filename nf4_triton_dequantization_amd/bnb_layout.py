@@ -302,3 +302,156 @@ class Embedding4bit(nn.Module):
         lin.weight = self.weight
         lin.bias = None
         return lin
+
+
+class Experts4bit(nn.Module):
+    """The experts of one projection of a mixture-of-experts block (Mixtral's w1, w2 or w3 over
+    all experts) as stacked NF4 storage: E weights of one shape ``[out_features, in_features]``,
+    blocksize 64, all with nested statistics or all with fp32 ``absmax``.
+
+    Storage (what ``kernel.nf4_moe_linear_bnb`` hands to the ``nf4_gemm_bnb_moe`` entry as base
+    pointers and strides), every expert's part exactly the bytes of its own
+    ``Linear4bit.from_float`` -- own absmax2 groups, own offset:
+
+    * ``weight``  uint8 ``[E, N*K/2]`` (a frozen parameter);
+    * ``absmax``  ``[E, N*K/64]``, uint8 (nested) or fp32 (``compress_statistics=False``);
+    * ``absmax2`` fp32 ``[E, ceil(N*K/64 / 256)]``, ``code2`` fp32 ``[256]`` shared by all
+      experts and ``offset`` fp32 ``[E]`` (nested; None otherwise).
+
+    ``expert(e)`` is a bias-free ``Linear4bit`` over views of that storage, so
+    ``dequantize_nf4_bnb(experts.expert(e))`` and ``nf4_linear_bnb(x, experts.expert(e))`` are
+    the reference for ``forward``.  The weights are frozen: no gradient reaches them.
+    """
+
+    def __init__(self, in_features: int, out_features: int, packed: torch.Tensor, absmax: torch.Tensor,
+                 absmax2: Optional[torch.Tensor], code2: Optional[torch.Tensor], offset: Optional[torch.Tensor],
+                 dtype: torch.dtype, blocksize2: int = 256):
+        super().__init__()
+        self.in_features, self.out_features = int(in_features), int(out_features)
+        self.num_experts = int(packed.shape[0])
+        self.blocksize, self.blocksize2 = 64, int(blocksize2)
+        self.dtype = dtype
+        N, K, E = self.out_features, self.in_features, self.num_experts
+        nblk = N * K // 64
+        self.nested = absmax.dtype == torch.uint8
+        if N * K % 64 or tuple(packed.shape) != (E, N * K // 2) or packed.dtype != torch.uint8:
+            raise ValueError(f"Experts4bit: packed must be uint8 [{E}, {N * K // 2}], got {packed.dtype} "
+                             f"{tuple(packed.shape)}")
+        if tuple(absmax.shape) != (E, nblk) or absmax.dtype not in (torch.uint8, torch.float32):
+            raise ValueError(f"Experts4bit: absmax must be uint8 or float32 [{E}, {nblk}], got {absmax.dtype} "
+                             f"{tuple(absmax.shape)}")
+        if self.nested:
+            n2 = (nblk + self.blocksize2 - 1) // self.blocksize2
+            if absmax2 is None or code2 is None or offset is None:
+                raise ValueError("Experts4bit: nested statistics need absmax2, code2 and offset")
+            if tuple(absmax2.shape) != (E, n2) or code2.numel() != 256 or offset.numel() != E:
+                raise ValueError(f"Experts4bit: expected absmax2 [{E}, {n2}], code2 [256] and offset [{E}], got "
+                                 f"{tuple(absmax2.shape)}, {tuple(code2.shape)}, {tuple(offset.shape)}")
+        else:
+            absmax2 = code2 = offset = None
+        self.weight = nn.Parameter(packed.contiguous(), requires_grad=False)
+        self.absmax = absmax.contiguous()
+        self.absmax2 = None if absmax2 is None else absmax2.to(torch.float32).contiguous()
+        self.code2 = None if code2 is None else code2.to(torch.float32).contiguous().view(256)
+        self.offset = None if offset is None else offset.to(torch.float32).contiguous().view(E)
+
+    @classmethod
+    def from_modules(cls, modules) -> "Experts4bit":
+        """Stack existing ``Linear4bit`` modules (copies).  They must have one shape, one
+        ``quant_state.dtype``, blocksize 64, no bias in use here (a bias is not carried), and all
+        nested statistics (one blocksize2, one code2 table) or all fp32 ones: else ``ValueError``."""
+        mods = list(modules)
+        if not mods:
+            raise ValueError("Experts4bit.from_modules: no modules")
+        first = mods[0]
+        qs0 = first.weight.quant_state
+        N, K = int(first.out_features), int(first.in_features)
+        nested0 = getattr(qs0, "state2", None) is not None and qs0.absmax.dtype == torch.uint8
+        for i, m in enumerate(mods):
+            qs = m.weight.quant_state
+            nested = getattr(qs, "state2", None) is not None and qs.absmax.dtype == torch.uint8
+            if (int(m.out_features), int(m.in_features)) != (N, K):
+                raise ValueError(f"Experts4bit.from_modules: expert {i} is {int(m.out_features)} x {int(m.in_features)}, "
+                                 f"expert 0 is {N} x {K}")
+            if qs.dtype != qs0.dtype:
+                raise ValueError(f"Experts4bit.from_modules: expert {i} has dtype {qs.dtype}, expert 0 {qs0.dtype}")
+            if int(qs.blocksize) != 64:
+                raise ValueError(f"Experts4bit.from_modules: expert {i} has blocksize {int(qs.blocksize)}, expected 64")
+            if nested != nested0:
+                raise ValueError("Experts4bit.from_modules: nested and fp32 statistics mixed")
+            if m.weight.data.dtype != torch.uint8 or m.weight.data.numel() != N * K // 2 or N * K % 64:
+                raise ValueError(f"Experts4bit.from_modules: expert {i}'s packed weight is not uint8 of N*K/2 bytes")
+            if nested and (int(qs.state2.blocksize) != int(qs0.state2.blocksize)
+                           or not torch.equal(qs.state2.code.to(qs0.state2.code.device), qs0.state2.code)):
+                raise ValueError(f"Experts4bit.from_modules: expert {i} has another blocksize2 or code2 table")
+        packed = torch.stack([m.weight.data.reshape(-1) for m in mods])
+        absmax = torch.stack([m.weight.quant_state.absmax.reshape(-1) for m in mods])
+        if not nested0:
+            return cls(K, N, packed, absmax.to(torch.float32), None, None, None, qs0.dtype)
+        dev = packed.device
+        absmax2 = torch.stack([m.weight.quant_state.state2.absmax.reshape(-1).to(torch.float32) for m in mods])
+        offs = []
+        for m in mods:
+            off = m.weight.quant_state.offset
+            if off is None:
+                off = 0.0
+            offs.append(off.reshape(()).to(device=dev, dtype=torch.float32) if torch.is_tensor(off)
+                        else torch.tensor(float(off), dtype=torch.float32, device=dev))
+        return cls(K, N, packed, absmax, absmax2, qs0.state2.code.clone(), torch.stack(offs), qs0.dtype,
+                   int(qs0.state2.blocksize))
+
+    @classmethod
+    def from_float(cls, weights, compute_dtype=None, compress_statistics: bool = True) -> "Experts4bit":
+        """Quantize an ``[E, N, K]`` float tensor, or a list of ``nn.Linear`` modules / ``[N, K]``
+        weights, one expert at a time through the HIP quantizer (``quantize.nf4_quantize``): the
+        stacked bytes are those of E separate ``Linear4bit.from_float`` calls.  ``dtype`` (what
+        ``forward`` returns) is ``compute_dtype`` if given, else the weights' dtype."""
+        if torch.is_tensor(weights):
+            if weights.dim() != 3:
+                raise ValueError(f"Experts4bit.from_float: expected an [E, out_features, in_features] tensor, got "
+                                 f"{tuple(weights.shape)}")
+            items = list(weights.unbind(0))
+        else:
+            items = [w.weight if isinstance(w, nn.Module) else w for w in weights]
+        return cls.from_modules([Linear4bit.from_float(w, compute_dtype=compute_dtype,
+                                                       compress_statistics=compress_statistics, bias=None)
+                                 for w in items])
+
+    def _apply(self, fn, recurse=True):
+        super()._apply(fn, recurse)
+        dev = self.weight.device
+        for name in ("absmax", "absmax2", "code2", "offset"):
+            t = getattr(self, name)
+            if t is not None and t.device != dev:
+                setattr(self, name, t.to(dev))
+        return self
+
+    def expert(self, e: int) -> Linear4bit:
+        """Expert ``e`` as a bias-free ``Linear4bit`` over VIEWS of this module's storage (no
+        copy), as ``Embedding4bit.as_linear()`` gives the tied head."""
+        e = int(e)
+        if not 0 <= e < self.num_experts:
+            raise IndexError(f"Experts4bit.expert: {e} outside 0..{self.num_experts - 1}")
+        N, K = self.out_features, self.in_features
+        if self.nested:
+            state2 = QuantState(absmax=self.absmax2[e], code=self.code2, blocksize=self.blocksize2, quant_type=None,
+                                dtype=torch.float32)
+            qs = QuantState(absmax=self.absmax[e], shape=torch.Size((N, K)), code=NF4_CODE.to(self.weight.device),
+                            blocksize=64, quant_type="nf4", dtype=self.dtype, offset=self.offset[e], state2=state2)
+        else:
+            qs = QuantState(absmax=self.absmax[e], shape=torch.Size((N, K)), code=NF4_CODE.to(self.weight.device),
+                            blocksize=64, quant_type="nf4", dtype=self.dtype)
+        lin = Linear4bit.__new__(Linear4bit)
+        nn.Module.__init__(lin)
+        lin.in_features, lin.out_features = K, N
+        lin.compute_dtype = self.dtype
+        lin.weight = Params4bit(self.weight.data[e].view(-1, 1), qs)
+        lin.bias = None
+        return lin
+
+    def forward(self, x: torch.Tensor, expert_ids: torch.Tensor) -> torch.Tensor:
+        """``y[t, j] = x[t] @ W_{expert_ids[t, j]}.t()`` (``x`` ``[T, K]``) or ``x[t, j] @ ...``
+        (``x`` ``[T, k, K]``): ``kernel.nf4_moe_linear_bnb``."""
+        from .kernel import nf4_moe_linear_bnb
+
+        return nf4_moe_linear_bnb(x, self, expert_ids)

@@ -25,7 +25,9 @@ Extensions beyond the reference: ``dequantize_nf4_many`` (one
 launch for many weights), ``dequantize_nf4_bnb`` (bitsandbytes semantics,
 parity unpinned), ``dequantize_nf4_into`` (caller-provided output) and the
 consumer ``x @ W.t()`` fused: ``nf4_linear`` / ``nf4_linear_grouped`` (reference
-semantics) and ``nf4_linear_bnb`` (bitsandbytes semantics, what ``Linear4bit.forward`` runs).
+semantics) and ``nf4_linear_bnb`` (bitsandbytes semantics, what ``Linear4bit.forward`` runs);
+``nf4_moe_linear_bnb`` runs one projection of a mixture-of-experts block for all experts
+(``Experts4bit``) in one launch, routed on the device.
 """
 from __future__ import annotations
 
@@ -911,4 +913,104 @@ def nf4_linear_bnb_grouped(x: torch.Tensor, modules: Sequence,
         if b is not None:
             y = y + b.to(y.dtype)
         out.append(y.reshape(*lead, int(mod.out_features)))
+    return out
+
+
+def _moe_fallback(x3: torch.Tensor, experts, ids: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """The per-expert loop over ``nf4_linear_bnb(x[idx], experts.expert(e))``.  It SYNCHRONISES
+    with the host: ``nonzero`` reads the routing back once per expert, so this route cannot be
+    captured in a graph.  Pairs whose id is outside ``0..E-1`` keep their rows of zeros."""
+    T, k = ids.shape
+    out.zero_()
+    flat = out.view(T * k, out.shape[-1])
+    xs = x3.expand(T, k, x3.shape[-1]).reshape(T * k, x3.shape[-1])
+    idf = ids.reshape(-1)
+    for e in range(experts.num_experts):
+        idx = (idf == e).nonzero().reshape(-1)  # host synchronisation
+        if idx.numel():
+            flat[idx] = nf4_linear_bnb(xs[idx], experts.expert(e)).to(flat.dtype)
+    return out
+
+
+def nf4_moe_linear_bnb(x: torch.Tensor, experts, expert_ids: torch.Tensor,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One projection of a mixture-of-experts block for all experts, in bitsandbytes semantics:
+    ``y[t, j] = x[t] @ W_e.t()`` with ``e = expert_ids[t, j]`` and ``W_e`` what
+    ``dequantize_nf4_bnb(experts.expert(e))`` returns, bit for bit.
+
+    ``experts`` is an ``Experts4bit``; ``expert_ids`` is ``[T, k]``, int32 or int64, on x's
+    device; ``x`` is ``[T, K]`` (the token's hidden state, shared by its k choices: Mixtral's w1
+    and w3) or ``[T, k, K]`` (per-pair activations: w2).  Returns ``[T, k, N]`` in ``experts.dtype``
+    (written into ``out`` when given: contiguous, that shape and dtype).  A pair whose id is
+    outside ``0..E-1`` gets a row of zeros, as ``nf4_embedding_bnb`` treats an id outside the
+    table; one token may name the same expert twice.
+
+    The fused route -- GPU tensors, fp16 / bf16, ``1 <= T*k <= MOE_MAX_PAIRS``, N % 64 == 0,
+    K % 128 == 0 and no gradient being recorded for ``x`` -- is ONE launch
+    (``nf4_gemm_bnb_moe``) plus at most a cast of the ids to int32: the ids and the offsets are
+    read on the device, never by the host, so ``torch.cuda.graph`` captures the call and a replay
+    follows whatever the router wrote into ``expert_ids`` since.  An expert without a pair costs
+    no weight traffic.  Everything else (more pairs, CPU tensors, a gradient for ``x``) takes the
+    per-expert loop over ``nf4_linear_bnb(x[idx], experts.expert(e))``, which SYNCHRONISES with
+    the host once per expert (it reads the routing back) and is therefore not capturable; autograd
+    follows it to ``x``.  Both routes use the same weights and fp32 accumulation; the summation
+    order differs, so the last bit of ``y`` may.
+    """
+    N, K, E = int(experts.out_features), int(experts.in_features), int(experts.num_experts)
+    dtype = experts.dtype
+    q = experts.weight.data
+    dev = q.device
+    if expert_ids.dim() != 2 or expert_ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"nf4_moe_linear_bnb: expert_ids must be int32 or int64 [T, k], got {expert_ids.dtype} "
+                         f"{tuple(expert_ids.shape)}")
+    T, k = int(expert_ids.shape[0]), int(expert_ids.shape[1])
+    if x.dim() == 2 and tuple(x.shape) == (T, K):
+        x_div, x3 = k, x.unsqueeze(1)
+    elif x.dim() == 3 and tuple(x.shape) == (T, k, K):
+        x_div, x3 = 1, x
+    else:
+        raise RuntimeError(f"nf4_moe_linear_bnb: x must be [{T}, {K}] or [{T}, {k}, {K}], got {tuple(x.shape)}")
+    if x.device != dev or expert_ids.device != dev:
+        raise RuntimeError(f"Expected all tensors to be on the same device, but found at least two devices, "
+                           f"{dev} and {x.device if x.device != dev else expert_ids.device}!")
+    if out is None:
+        out = torch.empty((T, k, N), dtype=dtype, device=dev)
+    elif tuple(out.shape) != (T, k, N) or out.dtype != dtype or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"nf4_moe_linear_bnb: out must be a contiguous {dtype} [{T}, {k}, {N}] tensor on {dev}")
+    P = T * k
+    if P == 0:
+        return out
+    fused = (dev.type == "cuda" and dtype in (torch.float16, torch.bfloat16) and 1 <= P <= _lib.MOE_MAX_PAIRS
+             and N % 64 == 0 and N >= 64 and K % 128 == 0 and K >= 128 and 1 <= E <= _lib.MOE_MAX_EXPERTS
+             and int(experts.blocksize) == 64 and q.dtype == torch.uint8 and q.is_contiguous()
+             and q.data_ptr() % 16 == 0 and (N * K // 2) % 16 == 0
+             and not (torch.is_grad_enabled() and x.requires_grad))
+    if not fused:
+        return _moe_fallback(x3, experts, expert_ids, out)
+    xc = x if x.dtype == dtype else x.to(dtype)
+    xc = xc.contiguous()
+    if xc.data_ptr() % 16:
+        xc = xc.clone()  # a view at an odd offset: the entry loads 16 bytes at a time
+    ids = expert_ids if expert_ids.dtype == torch.int32 else expert_ids.to(torch.int32)
+    ids = ids.contiguous()
+    nested = bool(experts.nested)
+    _on_device(dev, experts.absmax)
+    am = experts.absmax
+    if nested:
+        _on_device(dev, experts.absmax2, experts.code2, experts.offset)
+        desc = _lib.MoeExperts(q.data_ptr(), q.stride(0), am.data_ptr(), am.stride(0), experts.code2.data_ptr(), 0,
+                               experts.absmax2.data_ptr(), experts.absmax2.stride(0), experts.offset.data_ptr(),
+                               N, K, E, 0, 64, int(experts.blocksize2))
+    else:
+        desc = _lib.MoeExperts(q.data_ptr(), q.stride(0), None, 0, None, 0, am.data_ptr(), am.stride(0), None,
+                               N, K, E, 1, 64, 0)
+    L = _lib.lib()
+    dp = ctypes.cast(ctypes.pointer(desc), ctypes.c_void_p)
+    with torch.cuda.device(dev):
+        ws_bytes = L.nf4_gemm_bnb_moe_workspace_bytes(P, dp, None)
+        ws = _gemm_workspace(dev, ws_bytes) if ws_bytes else None
+        rc = L.nf4_gemm_bnb_moe(xc.data_ptr(), ids.data_ptr(), P, x_div, dp, out.data_ptr(), _dtype_code(dtype),
+                                ws.data_ptr() if ws is not None else None, ws_bytes, None,
+                                torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "nf4 fused moe gemm")
     return out
