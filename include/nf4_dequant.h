@@ -527,6 +527,51 @@ int nf4_gemm_bnb_moe(const void* x, const void* expert_ids, int64_t P, int32_t x
                      void* y, int32_t out_dtype, void* workspace, size_t workspace_bytes,
                      const nf4_gemm_cfg* cfg, void* hip_stream);
 
+/* The first half of a Llama-family MLP, `silu(gate(x)) * up(x)`, in bitsandbytes semantics for
+ * 1..128 rows: ONE launch of the row-tiled family over the gate and the up weight, which share
+ * x and the shape [I][K].  With dt = out_dtype (fp16 / bf16) and rn = round-to-nearest-even to dt,
+ *   g = rn(x . Wg^T)   u = rn(x . Wu^T)      exactly what nf4_gemm_bnb_mt stores for each weight
+ *   s = rn(g / (1.0f + expf(-g)))             fp32, IEEE division, never a fused multiply-add
+ *   h = rn(s * u)                             the fp32 product of two 16-bit values is exact
+ * -- the rounding chain of `F.silu(gate(x)) * up(x)` on 16-bit tensors; Wg / Wu bit for bit what
+ * nf4_dequant_bnb / nf4_dequant_bnb_single write.  A non-finite g or u gives whatever the chain
+ * gives.  A wave owns 16 columns of h: its two strips are the same 16 rows of the gate and of
+ * the up weight, so g and u of an element meet in one lane and neither makes a trip through
+ * memory.
+ * `gate_up` points at TWO nf4_gemm_bnb_mat in host memory, the gate weight then the up weight
+ * (`const void*`, as in nf4_gemm_bnb_grouped); they are not interchangeable.  Each has its own
+ * statistics, code2 table, offset (ONE fp32 ON THE DEVICE, NULL = 0) and blocksize2; both are
+ * nested (single == 0) or both have fp32 statistics (single != 0: absmax_q, code2, offset and
+ * blocksize2 are ignored).  Both N fields must equal I; the y fields are ignored.  `act` names
+ * the activation: NF4DQ_ACT_SILU (any other: NF4DQ_ERR_ARG).  h is [M][I], dense.
+ * Rules: nf4_gemm_bnb_mt's, per weight -- 1 <= M <= NF4DQ_GEMM_MT_MAX_M, I % 64 == 0 and
+ * I >= 64, K % 128 == 0 and K >= 128, the two N equal, packed_len == I*K/2, blocksize == 64 (a
+ * larger valid one: NF4DQ_ERR_SHAPE), nb / n2 as there; else NF4DQ_ERR_SHAPE.  I > 2^18 and the
+ * other size limits of nf4_gemm_bnb_mt: NF4DQ_ERR_TOO_LARGE.  A null pointer (offset excepted),
+ * x / packed not 16-byte or h not 8-byte aligned, a bad dtype, a block size that is no power of
+ * two: NF4DQ_ERR_ARG.
+ * cfg NULL = the library's choice.  A cfg names kernel NF4DQ_GEMM_MT_SWIGLU (0 = the same) with
+ *   waves   waves per workgroup, 2 / 4: a workgroup owns 16 * waves columns of h
+ *   depth   K stage in 128-deep chunks: 1
+ *   ksplit  K slices, 1 .. min(K / 128, 16); the last slices may be short or empty
+ *   strips  16-row weight strips per wave: 2 (one of gate, one of up; 0 = 2)
+ * and never falls back: an invalid one is NF4DQ_ERR_ARG.
+ * Workspace (nf4_gemm_bnb_mt_swiglu_workspace_bytes; 0 = none, one K slice): nf4_gemm_bnb_mt's
+ * layout and contract -- the ticket header, then per K slice the gate plane and the up plane of
+ * M * I floats ([ksplit][2][M][I]); 16-byte aligned, zero-filled before its first use, left zero
+ * by every call, one per stream, shareable with the other fused entries.  One ticket per column
+ * tile; the slice drawing the last one sums each plane in slice order, applies the chain, stores
+ * h and clears the planes and the ticket.  No workgroup waits for another, so the split-K error
+ * word is never set, and the result is a function of the inputs and the cfg alone.
+ * Asynchronous on `hip_stream`; one launch; allocates nothing; capturable in a graph. */
+#define NF4DQ_GEMM_MT_SWIGLU 10
+#define NF4DQ_ACT_SILU 0
+size_t nf4_gemm_bnb_mt_swiglu_workspace_bytes(int64_t M, int64_t I, int64_t K, const nf4_gemm_cfg* cfg);
+int nf4_gemm_bnb_mt_swiglu(const void* x, int64_t M, int64_t K,
+                           const void* gate_up /* nf4_gemm_bnb_mat[2]: gate, up */, int32_t single,
+                           int32_t act, void* h, int32_t out_dtype,
+                           void* workspace, size_t workspace_bytes, const nf4_gemm_cfg* cfg, void* hip_stream);
+
 /* The split-K hand-off never hangs: a reducer that has polled a partner slice's
  * entries 2^16 times without seeing them gives up, reads them as NaN and sets a
  * sticky error word in the workspace header.  This call waits for `hip_stream`,

@@ -1014,3 +1014,127 @@ def nf4_moe_linear_bnb(x: torch.Tensor, experts, expert_ids: torch.Tensor,
                                 torch.cuda.current_stream().cuda_stream)
     _lib.check(rc, "nf4 fused moe gemm")
     return out
+
+
+# Rows at which nf4_swiglu_bnb takes the fused launch (nf4_gemm_bnb_mt_swiglu): exactly those M
+# of {1, 8, 32, 33, 48, 64, 96, 128} at which it measured faster than what a caller did before --
+# nf4_linear_bnb_grouped, then F.silu(g) * u: one grouped launch up to 32 rows, two row-tiled
+# launches above, two elementwise launches either way -- at 14336x4096 and at 11008x4096 by more
+# than the run-to-run spread of the rounds (profiles/gemm_mt_swiglu/).  That holds
+# from 33 rows up (1.42x - 1.64x at 48 .. 128 rows) and fails up to 32, where the grouped
+# small-M launch and its two elementwise launches take half to two thirds of the fused launch's
+# time: the row-tiled anatomy is the slower one there.  An empty range (MIN above MAX) would mean
+# the fused launch is reached through the C entry alone.
+SWIGLU_ROUTED_MIN_M = 33
+SWIGLU_ROUTED_MAX_M = 128
+
+
+def _swiglu_fused(x: torch.Tensor, gate_proj, up_proj, M: int, I: int, K: int) -> bool:
+    """nf4_swiglu_bnb's fused-path rules (its docstring)."""
+    qg, qu = gate_proj.weight.data, up_proj.weight.data
+    sg, su = gate_proj.weight.quant_state, up_proj.weight.quant_state
+    dev = qg.device
+    if not (dev.type == "cuda" and qu.device == dev and x.device == dev and sg.dtype == su.dtype
+            and sg.dtype in (torch.float16, torch.bfloat16)
+            and SWIGLU_ROUTED_MIN_M <= M <= min(SWIGLU_ROUTED_MAX_M, _lib.GEMM_MT_MAX_M) and M >= 1
+            and I % 64 == 0 and I >= 64 and K % 128 == 0 and K >= 128
+            and getattr(gate_proj, "bias", None) is None and getattr(up_proj, "bias", None) is None
+            and not (torch.is_grad_enabled() and x.requires_grad)):
+        return False
+    for q, qs in ((qg, sg), (qu, su)):
+        if not (getattr(qs, "quant_type", None) == "nf4" and int(qs.blocksize) == 64 and _bnb_gemm_blocksizes(qs)
+                and q.dtype == torch.uint8 and q.numel() == I * K // 2 and q.is_contiguous()
+                and q.data_ptr() % 16 == 0):
+            return False
+    return _bnb_nested(sg) == _bnb_nested(su)
+
+
+def nf4_swiglu_bnb(x: torch.Tensor, gate_proj, up_proj, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``F.silu(gate_proj(x)) * up_proj(x)`` -- the first half of a Llama-family MLP -- for two
+    ``Linear4bit`` weights of one shape ``[I, K]`` in bitsandbytes semantics.  Returns ``[..., I]``
+    in ``quant_state.dtype`` (written into ``out`` when given: that shape and dtype).
+
+    The result is the rounding chain of the expression on 16-bit tensors: ``g`` and ``u`` rounded
+    to the dtype as ``nf4_linear_bnb`` stores them, ``silu`` in fp32 rounded once, the product
+    rounded once.  The fused route is ONE launch (``nf4_gemm_bnb_mt_swiglu``): neither ``g`` nor
+    ``u`` makes a trip through memory, the offsets are read on the device, nothing synchronises
+    with the host and ``torch.cuda.graph`` captures the call.  It is taken when the weights are
+    on a GPU, the dtype is fp16 or bf16, both modules are nf4 with blocksize 64 and the same
+    ``[I, K]`` (I % 64 == 0, K % 128 == 0), both have nested statistics or both plain fp32
+    ``absmax``, neither has a bias, the packed data is uint8 of I * K / 2 bytes and 16-byte
+    aligned, no gradient is being recorded for ``x`` and
+    ``SWIGLU_ROUTED_MIN_M <= M <= SWIGLU_ROUTED_MAX_M`` rows.  Everything else -- CPU tensors,
+    other row counts, a bias, other block sizes, a recorded gradient -- is
+    ``F.silu(g) * u`` with ``g, u = nf4_linear_bnb_grouped(x, [gate_proj, up_proj], biases)``,
+    which autograd follows and which has the same definition; the GEMMs' summation order may
+    differ between the routes, so the last bit of ``g`` and ``u`` may.
+    """
+    I, K = int(gate_proj.out_features), int(gate_proj.in_features)
+    if (int(up_proj.out_features), int(up_proj.in_features)) != (I, K):
+        raise RuntimeError(f"nf4_swiglu_bnb: gate_proj is [{I}, {K}], up_proj "
+                           f"[{int(up_proj.out_features)}, {int(up_proj.in_features)}]")
+    if x.shape[-1] != K:
+        raise RuntimeError(f"nf4_swiglu_bnb: x has {x.shape[-1]} features, the weights expect {K}")
+    lead = x.shape[:-1]
+    M = x.numel() // K if K else 0
+    dtype = gate_proj.weight.quant_state.dtype
+    dev = gate_proj.weight.data.device
+    if out is not None and (tuple(out.shape) != (*lead, I) or out.dtype != dtype or out.device != x.device
+                            or not out.is_contiguous()):
+        raise ValueError(f"nf4_swiglu_bnb: out must be a contiguous {dtype} {[*lead, I]} tensor on {x.device}")
+    if not _swiglu_fused(x, gate_proj, up_proj, M, I, K):
+        g, u = nf4_linear_bnb_grouped(x, [gate_proj, up_proj],
+                                      [getattr(gate_proj, "bias", None), getattr(up_proj, "bias", None)])
+        h = torch.nn.functional.silu(g) * u
+        if out is None:
+            return h
+        out.copy_(h)
+        return out
+    xc = x.reshape(M, K)
+    if xc.dtype != dtype:
+        xc = xc.to(dtype)
+    xc = xc.contiguous()
+    if xc.data_ptr() % 16:
+        xc = xc.clone()  # a view at an odd offset: the entry loads 16 bytes at a time
+    h = out if out is not None else torch.empty((*lead, I), dtype=dtype, device=dev)
+    nested = _bnb_nested(gate_proj.weight.quant_state)
+    keep = []  # every temporary outlives the enqueue (the caching allocator reuses freed blocks)
+    mats = (_lib.GemmBnbMat * 2)()
+    with torch.cuda.device(dev):
+        for i, mod in enumerate((gate_proj, up_proj)):  # the descriptors of nf4_linear_bnb_grouped
+            q, qs = mod.weight.data, mod.weight.quant_state
+            qc, qp, qn = _flat_ptr(q)
+            if nested:
+                _on_device(dev, qs.absmax, qs.state2.code, qs.state2.absmax)
+                a1, ap, an = _flat_ptr(qs.absmax)
+                c2 = qs.state2.code
+                c2, cp, cn = _flat_ptr(c2 if c2.dtype == torch.float32 else c2.to(torch.float32))
+                a2 = qs.state2.absmax
+                a2, bp, bn = _flat_ptr(a2 if a2.dtype == torch.float32 else a2.to(torch.float32))
+                if cn != 256:
+                    raise RuntimeError(f"nf4_swiglu_bnb: state2.code has {cn} entries, expected 256")
+                off, op = _offset_ptr(qs.offset, dev)
+                keep.extend((qc, a1, c2, a2, off))
+                mats[i] = _lib.GemmBnbMat(qp, qn, ap, an, cp, bp, bn, op, 64, int(qs.state2.blocksize), None, I)
+            else:
+                _on_device(dev, qs.absmax)
+                am = qs.absmax
+                am, ap, an = _flat_ptr(am if am.dtype == torch.float32 else am.to(torch.float32))
+                keep.extend((qc, am))
+                mats[i] = _lib.GemmBnbMat(qp, qn, None, 0, None, ap, an, None, 64, 0, None, I)
+        L = _lib.lib()
+        ws_bytes = L.nf4_gemm_bnb_mt_swiglu_workspace_bytes(M, I, K, None)
+        ws = _gemm_workspace(dev, ws_bytes) if ws_bytes else None
+        rc = L.nf4_gemm_bnb_mt_swiglu(xc.data_ptr(), M, K, ctypes.cast(mats, ctypes.c_void_p), 0 if nested else 1,
+                                      _lib.ACT_SILU, h.data_ptr(), _dtype_code(dtype),
+                                      ws.data_ptr() if ws is not None else None, ws_bytes, None,
+                                      torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "nf4 fused swiglu gemm")
+    del keep
+    return h
+
+
+def nf4_mlp_bnb(x: torch.Tensor, gate_proj, up_proj, down_proj) -> torch.Tensor:
+    """``down_proj(F.silu(gate_proj(x)) * up_proj(x))`` for ``Linear4bit`` weights in bitsandbytes
+    semantics: ``nf4_linear_bnb(nf4_swiglu_bnb(x, gate_proj, up_proj), down_proj)`` and nothing else."""
+    return nf4_linear_bnb(nf4_swiglu_bnb(x, gate_proj, up_proj), down_proj)
