@@ -1,6 +1,6 @@
-"""The acceptance set of the fused SwiGLU epilogue, shared by test_gpu_gemm_mt_swiglu.py and
-test_gpu_swiglu_api.py (test_swiglu_cpu.py checks this module itself on the host, against
-torch's CPU chain).
+"""The acceptance set of the fused SwiGLU epilogue, shared by test_gpu_gemm_mt_swiglu.py,
+test_gpu_swiglu_api.py and test_gpu_gemm_activations.py (test_swiglu_cpu.py checks this module
+itself on the host, against torch's CPU chain).
 
 The epilogue is defined on two 16-bit values g and u:
 
@@ -17,6 +17,16 @@ Everything here is computed on the CPU in float64 from bit patterns alone:
   exact in float64, so this ``rn`` is computed exactly, ties to even).
 * such near-tie elements may be at most 1 % of a case's elements (the reference alone gives
   0.06 - 0.11 % for N(0, 2) draws).
+* the chain is fp32, so ``expf(-g)`` overflows to +inf once -g passes ln(FLT_MAX) = 88.7228 and
+  ``s = g / inf = -0`` from there on, where a float64 silu would still give about -88.7 * 3e-39
+  (a 16-bit subnormal in bf16).  ``silu64`` models that: exp(-g) at or above the fp32 overflow
+  threshold (2 - 2^-24) * 2^127 counts as +inf.  The 1-ulp freedom of ``expf`` cannot change the
+  outcome on either 16-bit grid: bf16 has no point near 88.7228 (its neighbours are 88.5, where
+  exp is 0.80 of FLT_MAX, and 89.0, where it is 1.32 of it), and fp16's neighbours 88.6875 and
+  88.75 give 0.965 and 1.028 of FLT_MAX, thousands of ulps from the threshold.
+* non-finite g or u are judged only under ``accept(..., nonfinite=True)``: there ``h`` must have
+  the class (NaN, +inf, -inf) that the same formula gives in numpy from an allowed 16-bit ``s``:
+  silu(+inf) = +inf, silu(-inf) = -inf / inf = NaN, inf * 0 = NaN, anything with a NaN is NaN.
 """
 from __future__ import annotations
 
@@ -27,6 +37,7 @@ from _gemm_cases import bits_to_f64
 _FMT = {"bf16": (8, -126), "f16": (11, -14)}  # significant bits, smallest normal exponent
 TIE_MARGIN = 2.0 ** -21
 NEAR_TIE_CAP = 0.01
+EXPF_OVERFLOW = (2.0 - 2.0 ** -24) * 2.0 ** 127  # fp32 RNE gives +inf from here on
 
 
 def neighbours(v, dt):
@@ -56,13 +67,19 @@ def to_bits(v, dt):
     if dt == "f16":
         with np.errstate(over="ignore"):
             return v.astype(np.float16).view(np.uint16)
-    return (v.astype(np.float32).view(np.uint32) >> 16).astype(np.uint16)
+    with np.errstate(over="ignore"):
+        return (v.astype(np.float32).view(np.uint32) >> 16).astype(np.uint16)
 
 
 def silu64(g):
+    """g / (1 + exp(-g)) in float64 with the fp32 overflow of ``expf`` modelled: where exp(-g) is
+    at or above the fp32 overflow threshold the chain's divisor is +inf and s = g / inf, a zero
+    with the sign of g (-0: only a negative g gets there); -inf gives -inf / inf = NaN."""
     g = np.asarray(g, np.float64)
-    with np.errstate(over="ignore"):
-        return g / (1.0 + np.exp(-g))
+    with np.errstate(over="ignore", invalid="ignore"):
+        e = np.exp(-g)
+        e = np.where(e >= EXPF_OVERFLOW, np.inf, e)
+        return g / (1.0 + e)
 
 
 def allowed_s(g_bits, dt):
@@ -76,16 +93,35 @@ def allowed_s(g_bits, dt):
     return np.where(near, lo, r), np.where(near, hi, r), near
 
 
-def accept(h_bits, g_bits, u_bits, dt, what=""):
+def _cls(v):
+    """0 finite, 1 +inf, 2 -inf, 3 NaN."""
+    return np.where(np.isnan(v), 3, np.where(v == np.inf, 1, np.where(v == -np.inf, 2, 0)))
+
+
+def accept(h_bits, g_bits, u_bits, dt, what="", nonfinite=False):
     """Fail unless every element of ``h_bits`` is in the acceptance set of (g_bits, u_bits) and
-    at most 1 % of the elements are near a tie.  Returns the near-tie fraction."""
+    at most 1 % of the elements are near a tie.  Returns the near-tie fraction.
+
+    Non-finite g or u fail unless ``nonfinite`` is set; then, at those elements alone, ``h`` must
+    have the class (NaN, +inf, -inf) of ``s * u`` for an allowed ``s`` (the 16-bit ``s`` of a
+    finite g; silu64's own value of a non-finite one).  Such a product is never finite."""
     h_bits, g_bits, u_bits = (np.asarray(a, np.uint16) for a in (h_bits, g_bits, u_bits))
     assert h_bits.shape == g_bits.shape == u_bits.shape, (what, h_bits.shape, g_bits.shape, u_bits.shape)
-    u = bits_to_f64(u_bits, dt)
-    assert np.isfinite(u).all() and np.isfinite(bits_to_f64(g_bits, dt)).all(), f"{what}: non-finite g or u"
-    sa, sb, near = allowed_s(g_bits, dt)
-    ha, hb = to_bits(rn16(sa * u, dt), dt), to_bits(rn16(sb * u, dt), dt)
+    g, u = bits_to_f64(g_bits, dt), bits_to_f64(u_bits, dt)
+    gfin = np.isfinite(g)
+    fin = gfin & np.isfinite(u)
+    assert nonfinite or fin.all(), f"{what}: non-finite g or u"
+    sa, sb, near = allowed_s(np.where(gfin, g_bits, np.uint16(0)), dt)
+    near = near & gfin
+    with np.errstate(invalid="ignore"):
+        sa, sb = np.where(gfin, sa, silu64(g)), np.where(gfin, sb, silu64(g))
+        pa, pb = sa * u, sb * u
+    ha, hb = (to_bits(rn16(np.where(fin, p, 0.0), dt), dt) for p in (pa, pb))
     ok = (h_bits == ha) | (h_bits == hb)
+    if not fin.all():
+        assert (_cls(pa)[~fin] != 0).all() and (_cls(pb)[~fin] != 0).all(), what
+        hc = _cls(bits_to_f64(h_bits, dt))
+        ok = np.where(fin, ok, (hc == _cls(pa)) | (hc == _cls(pb)))
     frac = float(near.mean())
     if not ok.all():
         bad = np.argwhere(~ok)

@@ -129,6 +129,59 @@ def test_the_acceptance_set_holds_torchs_cpu_chain_and_little_else(dt, dtype):
         accept(once, bits(g), bits(u), dt)
 
 
+@pytest.mark.parametrize("dt,dtype", [("bf16", torch.bfloat16), ("f16", torch.float16)])
+def test_the_acceptance_set_follows_the_fp32_chain_over_the_whole_16_bit_domain(dt, dtype):
+    """Past -g = ln(FLT_MAX) = 88.72 the chain's fp32 ``expf`` is +inf and s = g / inf = -0; a
+    float64 silu is still a 16-bit subnormal there in bf16.  torch's CPU chain ``F.silu(g) * u`` on
+    every bf16 g in [-110, -80] and [80, 110], every fp16 g in [-20, -15] (s leaves the fp16 grid),
+    +-65504 (the fp16 max; bf16's nearest), +-inf and NaN, each with u from {0, -0, 1, -3, max,
+    inf, NaN}: all in the acceptance set, non-finite ones by class.  Without the flag a non-finite
+    g or u is refused as before, and a -0 past the overflow is required, not merely allowed."""
+    from _swiglu_cases import accept, allowed_s
+    from _gemm_cases import bits_to_f64
+
+    bits = lambda t: t.contiguous().view(torch.int16).numpy().view(np.uint16)
+    allg = torch.arange(-(1 << 15), 1 << 15, dtype=torch.int32).to(torch.int16).view(dtype)
+    gf = allg.float()
+    if dt == "bf16":
+        grid = allg[((gf >= -110) & (gf <= -80)) | ((gf >= 80) & (gf <= 110))]
+        assert grid.numel() == 2 * 61              # spacing 0.5 over [80, 110], both signs
+    else:
+        grid = allg[(gf >= -20) & (gf <= -15)]
+        assert grid.numel() == 128 + 257           # spacing 2^-7 over [15, 16), 2^-6 over [16, 20]
+    edge = torch.tensor([65504.0, -65504.0, float("inf"), float("-inf"), float("nan")]).to(dtype)
+    gs = torch.cat([grid, edge])
+    fmax = torch.finfo(dtype).max
+    for uv in (0.0, -0.0, 1.0, -3.0, fmax, float("inf"), float("nan")):
+        uu = torch.full_like(gs, uv)
+        h = F.silu(gs) * uu
+        frac = accept(bits(h), bits(gs), bits(uu), dt, f"{dt} u = {uv}", nonfinite=True)
+        assert frac <= 0.01
+        if np.isfinite(uv):
+            accept(bits(F.silu(grid) * uu[:grid.numel()]), bits(grid), bits(uu[:grid.numel()]), dt, f"{dt} finite, u = {uv}")
+            with pytest.raises(AssertionError, match="non-finite g or u"):
+                accept(bits(h), bits(gs), bits(uu), dt, "no flag")
+    if dt == "bf16":  # the overflow itself: -88.5 keeps a nonzero s, -89.0 and everything below is -0
+        probe = torch.tensor([-88.5, -89.0, -90.0, -95.0, -104.0, -110.0]).to(dtype)
+        sa, sb, near = allowed_s(bits(probe), dt)
+        assert not near.any() and sa[0] < 0 and (sa[1:] == 0).all() and np.signbit(sa[1:]).all()
+        assert (bits(F.silu(probe))[1:] == 0x8000).all() and bits(F.silu(probe))[0] != 0x8000
+        one = torch.ones_like(probe)
+        with pytest.raises(AssertionError):  # the float64 silu's subnormal where the chain gives -0
+            accept(np.array([0x8287], np.uint16), bits(probe[1:2]), bits(one[1:2]), dt)
+    # classes: silu(+inf) = +inf, silu(-inf) = NaN, inf * 0 = NaN; a wrong class is refused
+    g3 = torch.tensor([float("inf"), float("-inf"), float("inf")]).to(dtype)
+    u3 = torch.tensor([2.0, 2.0, 0.0]).to(dtype)
+    want = F.silu(g3) * u3
+    assert bool(torch.isinf(want[0])) and bool(torch.isnan(want[1])) and bool(torch.isnan(want[2]))
+    accept(bits(want), bits(g3), bits(u3), dt, "classes", nonfinite=True)
+    for wrong in ([0.0, float("nan"), float("nan")], [float("inf"), float("-inf"), float("nan")],
+                  [float("inf"), float("nan"), 0.0], [float("-inf"), float("nan"), float("nan")]):
+        with pytest.raises(AssertionError):
+            accept(bits(torch.tensor(wrong).to(dtype)), bits(g3), bits(u3), dt, "wrong class", nonfinite=True)
+    assert np.isfinite(bits_to_f64(bits(grid), dt)).all()
+
+
 def test_backward_reaches_x():
     gate, up, down = _mlp(torch.bfloat16, True)
     x = torch.randn(4, K, generator=torch.Generator().manual_seed(5)).to(torch.bfloat16).requires_grad_()
