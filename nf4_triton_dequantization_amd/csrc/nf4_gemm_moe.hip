@@ -4,8 +4,10 @@
 //
 // y[p][N] = x[p / x_div][K] . W_e[N][K]^T with e = expert_ids[p] read ON THE DEVICE and W_e the
 // 16-bit weights nf4_dequant_bnb writes for expert e, bit for bit.  One launch covers every
-// expert; the anatomy is the row-tiled kernel's (nf4_gemm_mt.hip, whose header comment gives the
-// reasons for the clamped loads, the slot rotation and the register budget -- they hold here):
+// expert; the anatomy is the row-tiled family's (nf4_gemm_mt_dev.h, whose header comment gives the
+// reasons for the clamped loads, the slot rotation and the register budget -- they hold here).
+// The ring entry, the rotation, the decode, the MFMA call, the split-K hand-off and the reducer
+// are that header's; the chunk loop is this file's own, because of its run-time row-tile guards:
 //  * the grid is experts x column tiles x K slices, fixed by the host from (P, E, N, K, CUs);
 //    a workgroup (WV waves) owns ONE expert, 32 WV of its columns and one K slice;
 //  * every wave reads the P ids (two per lane, clamped in bounds) and ballots `id == expert`:
@@ -28,7 +30,7 @@
 //    to exactly one expert: stored once per column tile, directly or by the reducer.
 // Split-K: the row-tiled kernel's hand-off with the slab indexed by pair and one ticket per
 // (expert, column tile).  Nobody waits for anybody: there is no poll.
-#include "nf4_gemm_launch.h"
+#include "nf4_gemm_mt_dev.h"
 #include "nf4_gemm_moe_plan.h"
 
 namespace {
@@ -49,16 +51,6 @@ struct MoeArgs {
     uint32_t tiles, ksplit, cps, chunks;  // column tiles, K slices, chunks per slice, K / 128
     uint32_t sh2;           // log2(blocksize2)
 };
-
-// One chunk of a lane's two strips: the packed bytes and the raw statistics.
-struct MoeW {
-    u32x4 w[kMtStrips];
-    uint32_t qa[kMtStrips];
-    float qb[kMtStrips];
-};
-
-// Slot rotation of a staged row (nf4_gemm_mt.hip).
-__device__ __forceinline__ uint32_t moe_rot(uint32_t row) { return (row & 3u) | ((row & 4u) << 1); }
 
 // (the second launch bound, waves per SIMD: with two row tiles the kernel needs no more than 256
 // registers, so a CU holds two workgroups of 4 waves -- what the plan's K-slice rule counts on,
@@ -132,12 +124,12 @@ __global__ __launch_bounds__(64 * WV, MT <= 2 ? 2 : 1) void nf4_gemm_moe_kernel(
     __syncthreads();  // the pair list, ahead of the first gather
 
     // Loads run ahead of the MFMAs in registers, slots compile-time, chunk numbers past the
-    // slice's end clamped to its last chunk: as in nf4_gemm_mt.hip.
+    // slice's end clamped to its last chunk: as in nf4_gemm_mt_dev.h.
     constexpr int kWD = 4;
-    constexpr int kXS = NP > 8 || MT >= 8 ? 1 : 2;
+    constexpr int kXS = kMtXSets<MT, WV>;
     constexpr int NPR = kXS == 2 ? NP : NP / 2;  // one set: the stage in two halves, half the registers
     u32x4 xr[kXS][NPR];
-    MoeW w[kWD];
+    MtW w[kWD];
     const uint32_t n = c_end - c_begin;  // chunks of this slice
     auto chunk_at = [&](uint32_t i) { return c_begin + (i < n ? i : n - 1u); };
     // (staged rows >= cnt load the expert's last row again and are zeroed on their way into LDS:
@@ -158,7 +150,7 @@ __global__ __launch_bounds__(64 * WV, MT <= 2 ? 2 : 1) void nf4_gemm_moe_kernel(
             const uint32_t p = tid + piece * T, row = p >> 4, seg = p & 15u;
             if (piece * T / 256u < my_tiles) {  // the piece's row tile (wave-uniform): tiles the expert does not fill are never read
                 const u32x4 v = row < cnt ? xr[S][i] : u32x4{0u, 0u, 0u, 0u};  // rows >= cnt: zeros in LDS
-                *reinterpret_cast<u32x4*>(buf + row * kMtRowBytes + ((seg + moe_rot(row)) & 15u) * 16u) = v;
+                *reinterpret_cast<u32x4*>(buf + row * kMtRowBytes + ((seg + mt_rot(row)) & 15u) * 16u) = v;
             }
         }
     };
@@ -203,13 +195,13 @@ __global__ __launch_bounds__(64 * WV, MT <= 2 ? 2 : 1) void nf4_gemm_moe_kernel(
     __syncthreads();  // the tables and the first stage
 
     const char* t = reinterpret_cast<const char*>(lut);
-    const uint32_t rot = moe_rot(nl);  // row 16 mt + nl: the rotation depends on nl alone
+    const uint32_t rot = mt_rot(nl);  // row 16 mt + nl: the rotation depends on nl alone
     auto step = [&](auto J, uint32_t i) {
         constexpr int j = decltype(J)::value;
         const char* buf = smem + (uint32_t)(j & 1) * kBuf;
         wload(std::integral_constant<int, (j + 3) % kWD>{}, chunk_at(i + 3u));
         if constexpr (kXS == 1) xload(I0{}, chunk_at(i + 1u));
-        const MoeW& cur = w[j];
+        const MtW& cur = w[j];
         float sc[kMtStrips];
 #pragma unroll
         for (int nt = 0; nt < kMtStrips; ++nt) sc[nt] = block_scale<SM>(c2tab, cur.qa[nt], cur.qb[nt], off);
@@ -222,19 +214,7 @@ __global__ __launch_bounds__(64 * WV, MT <= 2 ? 2 : 1) void nf4_gemm_moe_kernel(
         };
         auto decode = [&](u32x4(&bw)[kMtStrips], int s) {
 #pragma unroll
-            for (int nt = 0; nt < kMtStrips; ++nt) {
-                const uint32_t wd = cur.w[nt][s];
-                const uint32_t hi4 = (wd >> 2) & 0x3C3C3C3Cu;
-                const uint32_t lo4 = (wd << 2) & 0x3C3C3C3Cu;
-                float v[8];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    v[2 * k] = *reinterpret_cast<const float*>(t + ((hi4 >> (8 * k)) & 0xFFu)) * sc[nt];
-                    v[2 * k + 1] = *reinterpret_cast<const float*>(t + ((lo4 >> (8 * k)) & 0xFFu)) * sc[nt];
-                }
-                // the exact weights nf4_dequant_bnb writes: fp32 product, RNE to 16 bits
-                bw[nt] = u32x4{pack2<DT>(v[0], v[1]), pack2<DT>(v[2], v[3]), pack2<DT>(v[4], v[5]), pack2<DT>(v[6], v[7])};
-            }
+            for (int nt = 0; nt < kMtStrips; ++nt) bw[nt] = mt_decode<DT>(t, cur.w[nt][s], sc[nt]);
         };
         constexpr int kAF = MT >= 8 ? 1 : 2;
         u32x4 af[kAF][MT], bw[2][kMtStrips];  // (af[.][mt] is read and used under the same mt < my_tiles)
@@ -256,16 +236,8 @@ __global__ __launch_bounds__(64 * WV, MT <= 2 ? 2 : 1) void nf4_gemm_moe_kernel(
             for (int mt = 0; mt < MT; ++mt) {
                 if ((uint32_t)mt < my_tiles) {  // wave-uniform: a row tile the expert does not fill
 #pragma unroll
-                    for (int nt = 0; nt < kMtStrips; ++nt) {
-                        if constexpr (DT == NF4DQ_BF16)
-                            acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                                __builtin_bit_cast(bf16x8, af[s & (kAF - 1)][mt]), __builtin_bit_cast(bf16x8, bw[s & 1][nt]),
-                                acc[mt][nt], 0, 0, 0);
-                        else
-                            acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                                __builtin_bit_cast(f16x8, af[s & (kAF - 1)][mt]), __builtin_bit_cast(f16x8, bw[s & 1][nt]),
-                                acc[mt][nt], 0, 0, 0);
-                    }
+                    for (int nt = 0; nt < kMtStrips; ++nt)
+                        acc[mt][nt] = mt_mfma<DT>(af[s & (kAF - 1)][mt], bw[s & 1][nt], acc[mt][nt]);
                 }
             }
         }
@@ -311,58 +283,11 @@ __global__ __launch_bounds__(64 * WV, MT <= 2 ? 2 : 1) void nf4_gemm_moe_kernel(
                 for (int nt = 0; nt < kMtStrips; ++nt) mine[at + 16u * nt] = acc[mt][nt][i];
             }
         }
-    // publish: every wave's stores done, then ONE agent-scope release ahead of the ticket
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint32_t ticket = __hip_atomic_fetch_add(A.counters + et, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool last = ticket == A.ksplit - 1u;
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_store(A.counters + et, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next call
-        }
-        *flag = last ? 1u : 0u;
-    }
-    __syncthreads();
-    if (*flag == 0u) return;
-    // the reducer: every slice's rows of this expert in slice order, 4 columns per thread and
-    // element, cleared behind it (nf4_gemm_mt.hip's, with the rows taken from the pair list)
-    constexpr int kE = 16 * MT * (int)(COLS / 4u) / (int)T;  // elements per thread at 16 MT rows
-    const uint32_t total = cnt * (COLS / 4u);
-    const uint32_t sstride = A.P * A.N;  // floats per slab; ksplit slabs < 2^30 floats: validated
-    uint32_t at[kE];
-    f32x4 sum[kE];
-#pragma unroll
-    for (int j = 0; j < kE; ++j) {
-        const uint32_t e0 = tid + (uint32_t)j * T, e = e0 < total ? e0 : total - 1u;
-        at[j] = prow[e / (COLS / 4u)] * A.N + tile * COLS + 4u * (e % (COLS / 4u));
-    }
-    for (uint32_t sl = 0; sl < A.ksplit; ++sl) {
-        f32x4 v[kE];
-#pragma unroll
-        for (int j = 0; j < kE; ++j) v[j] = *reinterpret_cast<const f32x4*>(A.slab + sl * sstride + at[j]);
-#pragma unroll
-        for (int j = 0; j < kE; ++j) {
-            if (sl == 0u) sum[j] = v[j];  // the first slice starts the sum: -0 stays -0
-            else {
-                sum[j].x += v[j].x;
-                sum[j].y += v[j].y;
-                sum[j].z += v[j].z;
-                sum[j].w += v[j].w;
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < kE; ++j)
-        if (tid + (uint32_t)j * T < total) {
-            for (uint32_t sl = 0; sl < A.ksplit; ++sl)
-                *reinterpret_cast<f32x4*>(A.slab + sl * sstride + at[j]) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-            u32x2* dst = reinterpret_cast<u32x2*>(reinterpret_cast<uint16_t*>(A.y) + at[j]);
-            *dst = u32x2{pack2<DT>(sum[j].x, sum[j].y), pack2<DT>(sum[j].z, sum[j].w)};
-        }
+    // publish, ticket, acquire and the slice-order reducer: the family's (nf4_gemm_mt_dev.h), with
+    // the rows taken from the pair list and the ticket of this (expert, column tile)
+    const MtJob job{A.x, A.y, A.slab, A.counters + et, smem, lut, flag, A.P, A.N, A.K, tile, ks, A.ksplit, A.cps, A.chunks};
+    if (mt_publish_last(job.ticket, A.ksplit, flag))
+        mt_reduce<DT, MT, WV, MtStrips<1>, MtSumOut<DT>>(job, MtListedRows{cnt, prow});
 }
 
 template <int SM>
@@ -378,8 +303,8 @@ int launch_moe(const nf4gemm::MoeCall& a, const nf4_gemm_cfg& cfg, hipStream_t s
     A.ids = reinterpret_cast<const int32_t*>(a.ids);
     A.x = a.x;
     A.y = a.y;
-    A.counters = reinterpret_cast<uint32_t*>(a.workspace);
-    A.slab = cfg.ksplit > 1 ? reinterpret_cast<float*>(reinterpret_cast<char*>(a.workspace) + kHeaderBytes) : nullptr;
+    A.counters = mt_counters(a.workspace);
+    A.slab = mt_slab(a.workspace, cfg);
     A.packed_stride = e.packed_stride;
     A.nb_stride = e.nb_stride;
     A.n2_stride = e.n2_stride;
@@ -393,7 +318,7 @@ int launch_moe(const nf4gemm::MoeCall& a, const nf4_gemm_cfg& cfg, hipStream_t s
     A.ksplit = (uint32_t)cfg.ksplit;
     A.cps = p.cps;
     A.chunks = p.chunks;
-    while (!e.single && (1 << A.sh2) < e.blocksize2) ++A.sh2;
+    A.sh2 = mt_log2_blocksize2(e.single, e.blocksize2);
     int rc = NF4DQ_ERR_ARG;
     pick<NF4DQ_BF16, NF4DQ_F16>(a.dtype, [&](auto DT) {
         pick<2, 4, 6, 8>((int)p.row_tiles, [&](auto MT) {

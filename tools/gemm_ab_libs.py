@@ -1,7 +1,8 @@
-"""Two builds of the library against each other in ONE process: the existing fused-GEMM
-entries (nf4_gemm_ref, nf4_gemm_ref_grouped, nf4_gemm_bnb), graph replay, interleaved rounds.
+"""Two builds of the library against each other in ONE process: the fused-GEMM entries of
+``--entries``, outputs compared bit for bit, then graph replay in interleaved rounds.
 
     python tools/gemm_ab_libs.py --a parent --b prod [--again parent2] [--ms 1,8,32] [--rounds 7]
+        [--entries nf4_gemm_bnb_mt,nf4_gemm_bnb_mt_swiglu,nf4_gemm_bnb_moe]
 
 ``--a`` / ``--b`` / ``--again``: ``prod`` (the product library) or the name of a
 tools/_build/libnf4dq_<name>.so.  ``--again`` is a second copy of build A under another file
@@ -11,7 +12,14 @@ weights larger than the Infinity Cache; per (entry, shape, M) the captured launc
 build are replayed in turn, ``rounds`` times.  ``grouped``: nf4_gemm_ref_grouped over the
 Llama q/k/v (4096, 1024, 1024) and gate/up (14336, 14336) groups at K = 4096.  One JSON line
 per point: per-launch medians, B over A, and the largest per-round deviation of A against its
-second copy.
+second copy.  ``nf4_gemm_bnb_mt`` and ``nf4_gemm_bnb_mt_swiglu`` (``--shapes`` are N,K and I,K)
+run over ``--ms``; ``nf4_gemm_bnb_moe`` over ``--moe`` ("experts,N,K,x_div;...") and ``--tokens``
+(two choices per token, drawn once).  All with the library's own cfg and the workspace each
+build asks for.  Before a point is timed every build runs it once on the same inputs into its
+own output.  For the three row-tiled entries any bit that differs from build A's ends the run:
+their sums run in MFMA order over the chunks and in slice order in the reducer in every build,
+so anything but equality is a behaviour change.  For the older entries, whose builds may
+legitimately order a sum differently, the line only reports ``bit_equal``.
 """
 from __future__ import annotations
 
@@ -29,13 +37,17 @@ from nf4_triton_dequantization_amd import _lib  # noqa: E402
 from tools.bench_gemm import _interleaved_rounds  # noqa: E402
 
 ENTRIES = ("nf4_gemm_ref", "nf4_gemm_ref_grouped", "nf4_gemm_bnb", "nf4_gemm_workspace_bytes",
-           "nf4_gemm_grouped_workspace_bytes", "nf4_gemm_bnb_workspace_bytes", "nf4_gemm_check_workspace")
+           "nf4_gemm_grouped_workspace_bytes", "nf4_gemm_bnb_workspace_bytes", "nf4_gemm_check_workspace",
+           "nf4_gemm_bnb_mt", "nf4_gemm_bnb_mt_workspace_bytes", "nf4_gemm_bnb_mt_swiglu",
+           "nf4_gemm_bnb_mt_swiglu_workspace_bytes", "nf4_gemm_bnb_moe", "nf4_gemm_bnb_moe_workspace_bytes")
 
 
 def load(name):
     path = _lib.LIB_PATH if name == "prod" else os.path.join(REPO, "tools", "_build", f"libnf4dq_{name}.so")
     h = ctypes.CDLL(path)
     for e in ENTRIES:
+        if not hasattr(h, e):  # a build from before the entry: fine while --entries does not ask for it
+            continue
         getattr(h, e).restype, getattr(h, e).argtypes = _lib.SIGNATURES[e]
     return h
 
@@ -49,7 +61,11 @@ def main():
     ap.add_argument("--shapes", default="4096,4096;14336,4096;4096,14336")
     ap.add_argument("--budget-mb", type=int, default=768)
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--entries", default="nf4_gemm_ref,nf4_gemm_bnb,nf4_gemm_ref_grouped")
+    ap.add_argument("--moe", default="8,14336,4096,2;8,4096,14336,1")
+    ap.add_argument("--tokens", default="1,16,64")
     args = ap.parse_args()
+    entries = [e for e in args.entries.split(",") if e]
     names = [args.a, args.b] + ([args.again] if args.again else [])
     libs = [load(n) for n in names]
     dev = torch.device("cuda", 0)
@@ -65,10 +81,12 @@ def main():
     code2 = torch.linspace(-1.0, 1.0, 256, device=dev)
     off = torch.full((1,), 0.01, device=dev)
 
-    def report(entry, what, M, n, ts):
+    EXACT = ("nf4_gemm_bnb_mt", "nf4_gemm_bnb_mt_swiglu", "nf4_gemm_bnb_moe")
+
+    def report(entry, what, M, n, ts, bit_equal):
         med = [sorted(t)[len(t) // 2] for t in ts]
         res = {"entry": entry, "what": what, "M": M, "launches": n, "a": names[0], "b": names[1],
-               "a_us": round(med[0], 3), "b_us": round(med[1], 3), "b_over_a": round(med[1] / med[0], 4),
+               "a_us": round(med[0], 3), "b_us": round(med[1], 3), "b_over_a": round(med[1] / med[0], 4), "bit_equal": bit_equal,
                "b_over_a_by_round": [round(b / a, 4) for a, b in zip(ts[0], ts[1])]}
         if len(ts) > 2:
             res["a_again_over_a_by_round"] = [round(c / a, 4) for a, c in zip(ts[0], ts[2])]
@@ -79,18 +97,122 @@ def main():
         for L in libs if wsz else ():  # a buffer no split-K ever ran on has nothing to report
             assert L.nf4_gemm_check_workspace(work.data_ptr(), work.numel(), torch.cuda.current_stream().cuda_stream) == 0
 
+    def point(entry, what, M, n, work, wsz, runs, outs):
+        """runs[i]: build i's n launches (the first into outs[i]).  Bit-equal outputs, then the rounds."""
+        same = True
+        for i, (run, out) in enumerate(zip(runs, outs)):
+            out.view(torch.int16).fill_(0x7FFF)  # NaN bits: a row nobody stores is seen
+            run()
+            torch.cuda.synchronize()
+            eq = torch.equal(out.view(torch.int16), outs[0].view(torch.int16))
+            assert eq or entry not in EXACT, \
+                f"{entry} {what} M={M}: build {names[i]} differs from {names[0]} in " \
+                f"{int((out.view(torch.int16) != outs[0].view(torch.int16)).sum())} elements"
+            same = same and eq
+        report(entry, what, M, n, _interleaved_rounds(runs, n, args.rounds), same)
+        check(work, wsz)
+
+    def bf16_out(M, n):
+        return [torch.empty((M, n), dtype=torch.bfloat16, device=dev) for _ in libs]
+
     ms = [int(v) for v in args.ms.split(",")]
-    for sh in [s for s in args.shapes.split(";") if s]:
-        n, k = (int(v) for v in sh.split(","))
+    shapes = [tuple(int(v) for v in s.split(",")) for s in args.shapes.split(";") if s]
+    if "nf4_gemm_bnb_mt" in entries:
+        for n, k in shapes:
+            copies = max(8, args.budget_mb * (1 << 20) // (n * k // 2))
+            ws = [weight(n, k) for _ in range(copies)]
+            for M in ms:
+                x = torch.randn((M, k), device=dev, generator=gen).to(torch.bfloat16)
+                ys = bf16_out(M, n)
+                wsz = max(L.nf4_gemm_bnb_mt_workspace_bytes(M, n, k, None) for L in libs)
+                work = torch.zeros(max(wsz, 1 << 17), dtype=torch.uint8, device=dev)
+
+                def mt(L, y):
+                    def run():
+                        sp = torch.cuda.current_stream().cuda_stream
+                        for (q, a1, a2) in ws:
+                            rc = L.nf4_gemm_bnb_mt(x.data_ptr(), M, q.data_ptr(), q.numel(), a1.data_ptr(), a1.numel(),
+                                                   code2.data_ptr(), a2.data_ptr(), a2.numel(), off.data_ptr(), 64, 256,
+                                                   y.data_ptr(), _lib.BF16, n, k, work.data_ptr(), work.numel(), None, sp)
+                            assert rc == 0, rc
+                    return run
+
+                point("nf4_gemm_bnb_mt", f"{n}x{k}", M, copies, work, wsz, [mt(L, y) for L, y in zip(libs, ys)], ys)
+            del ws
+    if "nf4_gemm_bnb_mt_swiglu" in entries:
+        code2u = torch.linspace(0.75, -0.75, 256, device=dev)
+        offu = torch.full((1,), -0.02, device=dev)
+        for n, k in shapes:
+            copies = max(8, args.budget_mb * (1 << 20) // (n * k))
+            ws = [(weight(n, k), weight(n, k)) for _ in range(copies)]
+            pairs = []
+            for g, u in ws:
+                mats = (_lib.GemmBnbMat * 2)()
+                for j, ((q, a1, a2), c2, o) in enumerate(((g, code2, off), (u, code2u, offu))):
+                    mats[j] = _lib.GemmBnbMat(q.data_ptr(), q.numel(), a1.data_ptr(), a1.numel(), c2.data_ptr(), a2.data_ptr(),
+                                              a2.numel(), o.data_ptr(), 64, 256, None, n)
+                pairs.append(mats)
+            for M in ms:
+                x = (torch.randn((M, k), device=dev, generator=gen) * 0.05).to(torch.bfloat16)
+                hs = bf16_out(M, n)
+                wsz = max(L.nf4_gemm_bnb_mt_swiglu_workspace_bytes(M, n, k, None) for L in libs)
+                work = torch.zeros(max(wsz, 1 << 17), dtype=torch.uint8, device=dev)
+
+                def sg(L, h):
+                    def run():
+                        sp = torch.cuda.current_stream().cuda_stream
+                        for mats in pairs:
+                            rc = L.nf4_gemm_bnb_mt_swiglu(x.data_ptr(), M, k, ctypes.cast(mats, ctypes.c_void_p), 0, _lib.ACT_SILU,
+                                                          h.data_ptr(), _lib.BF16, work.data_ptr(), work.numel(), None, sp)
+                            assert rc == 0, rc
+                    return run
+
+                point("nf4_gemm_bnb_mt_swiglu", f"{n}x{k}", M, copies, work, wsz, [sg(L, h) for L, h in zip(libs, hs)], hs)
+            del ws, pairs
+    if "nf4_gemm_bnb_moe" in entries:
+        for E, n, k, x_div in [tuple(int(v) for v in s.split(",")) for s in args.moe.split(";") if s]:
+            copies = max(8, args.budget_mb * (1 << 20) // (E * n * k // 2))
+            nb, n2 = n * k // 64, (n * k // 64 + 255) // 256
+            stacks = []
+            for _ in range(copies):
+                q = torch.randint(0, 256, (E, n * k // 2), dtype=torch.uint8, device=dev, generator=gen)
+                a1 = torch.randint(0, 256, (E, nb), dtype=torch.uint8, device=dev, generator=gen)
+                a2 = torch.rand((E, n2), device=dev, generator=gen) * 0.01 + 1e-3
+                offs = torch.linspace(0.01, 0.02, E, device=dev)
+                d = _lib.MoeExperts(q.data_ptr(), n * k // 2, a1.data_ptr(), nb, code2.data_ptr(), 0, a2.data_ptr(), n2,
+                                    offs.data_ptr(), n, k, E, 0, 64, 256)
+                stacks.append((d, (q, a1, a2, offs)))
+            for tokens in [int(v) for v in args.tokens.split(",")]:
+                P = 2 * tokens  # two choices per token: w1 (x_div 2) reads the token's row twice, w2 a row per pair
+                ids = torch.randint(0, E, (P,), dtype=torch.int32, device=dev, generator=gen)
+                x = (torch.randn((-(-P // x_div), k), device=dev, generator=gen) * 0.05).to(torch.bfloat16)
+                ys = bf16_out(P, n)
+                wsz = max(L.nf4_gemm_bnb_moe_workspace_bytes(P, ctypes.cast(ctypes.pointer(stacks[0][0]), ctypes.c_void_p), None)
+                          for L in libs)
+                work = torch.zeros(max(wsz, 1 << 17), dtype=torch.uint8, device=dev)
+
+                def moe(L, y):
+                    def run():
+                        sp = torch.cuda.current_stream().cuda_stream
+                        for d, _ in stacks:
+                            rc = L.nf4_gemm_bnb_moe(x.data_ptr(), ids.data_ptr(), P, x_div, ctypes.cast(ctypes.pointer(d), ctypes.c_void_p),
+                                                    y.data_ptr(), _lib.BF16, work.data_ptr(), work.numel(), None, sp)
+                            assert rc == 0, rc
+                    return run
+
+                point("nf4_gemm_bnb_moe", f"{E}x{n}x{k} x_div={x_div}", P, copies, work, wsz,
+                      [moe(L, y) for L, y in zip(libs, ys)], ys)
+            del stacks
+    for n, k in shapes if ("nf4_gemm_ref" in entries or "nf4_gemm_bnb" in entries) else ():
         copies = max(8, args.budget_mb * (1 << 20) // (n * k // 2))
         ws = [weight(n, k) for _ in range(copies)]
         for M in ms:
             x = torch.randn((M, k), device=dev, generator=gen).to(torch.bfloat16)
-            y = torch.empty((M, n), dtype=torch.bfloat16, device=dev)
+            ys = bf16_out(M, n)
             wsz = max(max(L.nf4_gemm_workspace_bytes(M, n, k), L.nf4_gemm_bnb_workspace_bytes(M, n, k, None)) for L in libs)
             work = torch.zeros(max(wsz, 1 << 17), dtype=torch.uint8, device=dev)
 
-            def ref(L):
+            def ref(L, y):
                 def run():
                     sp = torch.cuda.current_stream().cuda_stream
                     for (q, a1, a2) in ws:
@@ -100,7 +222,7 @@ def main():
                         assert rc == 0, rc
                 return run
 
-            def bnb(L):
+            def bnb(L, y):
                 def run():
                     sp = torch.cuda.current_stream().cuda_stream
                     for (q, a1, a2) in ws:
@@ -110,12 +232,13 @@ def main():
                         assert rc == 0, rc
                 return run
 
-            report("nf4_gemm_ref", f"{n}x{k}", M, copies, _interleaved_rounds([ref(L) for L in libs], copies, args.rounds))
-            report("nf4_gemm_bnb", f"{n}x{k}", M, copies, _interleaved_rounds([bnb(L) for L in libs], copies, args.rounds))
-            check(work, wsz)
+            if "nf4_gemm_ref" in entries:
+                point("nf4_gemm_ref", f"{n}x{k}", M, copies, work, wsz, [ref(L, y) for L, y in zip(libs, ys)], ys)
+            if "nf4_gemm_bnb" in entries:
+                point("nf4_gemm_bnb", f"{n}x{k}", M, copies, work, wsz, [bnb(L, y) for L, y in zip(libs, ys)], ys)
         del ws
     k = 4096
-    for label, ns in (("qkv", (4096, 1024, 1024)), ("gate_up", (14336, 14336))):
+    for label, ns in (("qkv", (4096, 1024, 1024)), ("gate_up", (14336, 14336))) if "nf4_gemm_ref_grouped" in entries else ():
         copies = max(8, args.budget_mb * (1 << 20) // (sum(ns) * k // 2))
         groups, keep = [], []
         ys = None
@@ -144,7 +267,7 @@ def main():
                 return run
 
             report("nf4_gemm_ref_grouped", label, M, copies,
-                   _interleaved_rounds([grouped(L) for L in libs], copies, args.rounds))
+                   _interleaved_rounds([grouped(L) for L in libs], copies, args.rounds), None)  # shared outputs: not compared
             check(work, wsz)
 
 

@@ -1,0 +1,155 @@
+"""Device assembly and resource usage of the row-tiled GEMM family (nf4_gemm_mt.hip,
+nf4_gemm_mt_swiglu.hip, nf4_gemm_moe.hip), and one tree's kernels against another's.
+
+    python tools/gemm_mt_family_asm.py --out DIR [--csrc DIR] [--tables] [--against DIR]
+
+Compiles the three sources of ``--csrc`` (default: this tree's) to device assembly with the
+Makefile's flags (``--cuda-device-only -S -Rpass-analysis=kernel-resource-usage``, without
+-Werror) into ``--out``.  ``--tables`` rewrites profiles/gemm_{mt,mt_swiglu,moe}/resource_usage.txt
+from the compiler's remarks.  ``--against DIR`` (an ``--out`` of another tree, e.g. the parent
+commit's sources) compares kernel by kernel: the instruction streams after dropping comments and
+directives and renumbering labels, and where they differ scratch, spills, waves per SIMD,
+AGPRs, the LDS bytes the compiler reports and the v_mfma count; it exits 1 when one of those
+differs.  These kernels' LDS is all dynamic, so the compiler reports 0 and the tables' LDS
+column is the launch's size as the plan headers compute it (`*_lds_bytes`), not a measurement:
+a change of it shows in the plan snapshot tests, not here.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import re
+import subprocess
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(REPO, "nf4_triton_dequantization_amd")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")  # the Makefile's default
+
+
+def makefile_flags():
+    """The Makefile's HIPFLAGS for gfx950 without -Werror (it turns the driver's unused
+    --hip-link into an error in this mode), plus what makes assembly and remarks."""
+    text = open(os.path.join(PKG, "Makefile")).read().replace("\\\n", " ")
+    flags = re.search(r"^HIPFLAGS \?= (.*)$", text, re.M).group(1).replace("$(ARCH)", "gfx950").split()
+    return [f for f in flags if f != "-Werror"] + ["--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage"]
+
+
+FLAGS = makefile_flags()
+# source -> (profiles directory, kernel, bytes of tables behind the x buffers: the plan headers' k*TableBytes)
+FAMILY = {"nf4_gemm_mt": ("gemm_mt", "nf4_gemm_mt_kernel", 1104),
+          "nf4_gemm_mt_swiglu": ("gemm_mt_swiglu", "nf4_gemm_mt_swiglu_kernel", 2128),
+          "nf4_gemm_moe": ("gemm_moe", "nf4_gemm_moe_kernel", 2128)}
+FIELDS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch",
+          "Occupancy [waves/SIMD]": "waves", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill",
+          "LDS Size [bytes/block]": "static_lds"}
+
+
+def compile_all(csrc, out):
+    os.makedirs(out, exist_ok=True)
+    procs = []
+    for src in FAMILY:
+        log = open(os.path.join(out, src + ".log"), "w")
+        cmd = [HIPCC, *FLAGS, "-I", os.path.join(REPO, "include"), "-o", os.path.join(out, src + ".s"),
+               os.path.join(csrc, src + ".hip")]
+        procs.append((src, subprocess.Popen(cmd, stdout=log, stderr=subprocess.STDOUT)))
+    for src, p in procs:
+        if p.wait() != 0:
+            sys.exit(f"{src}: compile failed, see {out}/{src}.log")
+
+
+def kernels(out, src):
+    """{mangled name: {resources, insts}} of one compiled source."""
+    res, name = {}, None
+    for line in open(os.path.join(out, src + ".log")):
+        m = re.search(r"remark:\s+(.*?): (\S+) \[-Rpass", line)
+        if not m:
+            continue
+        if m.group(1) == "Function Name":
+            name = m.group(2)
+            res[name] = {"insts": []}
+        elif m.group(1) in FIELDS:
+            res[name][FIELDS[m.group(1)]] = int(m.group(2))
+    cur = None
+    for line in open(os.path.join(out, src + ".s")):
+        line = line.split(";")[0].rstrip()
+        assert "s_swappc" not in line, f"{src}: a call in device code -- a pipeline stage was not inlined"
+        m = re.match(r"^(\w+):$", line)
+        if m and m.group(1) in res:
+            cur, labels = res[m.group(1)]["insts"], {}
+        elif cur is not None and line.startswith(".Lfunc_end"):
+            cur = None
+        elif cur is not None and re.match(r"^\s+[a-z]\w*", line):
+            cur.append(re.sub(r"\.LBB\d+_\d+", lambda l: labels.setdefault(l.group(0), f".L{len(labels)}"), line.strip()))
+    return res
+
+
+def params(name):
+    dt, mt, sm, wv = (int(v) for v in re.search(r"kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E", name).groups())
+    return dt, mt, sm, wv
+
+
+def write_table(out, src):
+    prof, kernel, tables = FAMILY[src]
+    ks = kernels(out, src)
+    rows = [f"{kernel}<DT, MT, SM, WV>: hipcc {' '.join(f for f in FLAGS if f not in ('-fPIC', '-Wall', '-S', '--cuda-device-only'))}",
+            f"(LDS is dynamic: two x buffers of 16 MT rows x 256 bytes + {tables} bytes behind them; static LDS 0."
+            "  Columns: the compiler's remarks; SGPRs = TotalSGPRs; spills: SGPR + VGPR; LDS bytes: computed as the"
+            " plan header does, not measured)", "",
+            "dtype row_tiles mode    waves  VGPRs  AGPRs  SGPRs  scratch  spills  waves/SIMD  LDS bytes  v_mfma"]
+    for sm in (2, 1):  # kScaleBnbSingle, kScaleBnb
+        for dt in (1, 0):  # NF4DQ_BF16, NF4DQ_F16
+            for name, k in sorted(ks.items(), key=lambda it: (params(it[0])[1], -params(it[0])[3])):
+                d, mt, s, wv = params(name)
+                if (d, s) != (dt, sm):
+                    continue
+                assert k["static_lds"] == 0
+                rows.append(f"{'bf16' if dt else 'f16':<5}{mt:>10} {'nested' if sm == 1 else 'single':<7}{wv:>6}"
+                            f"{k['vgprs']:>7}{k['agprs']:>7}{k['sgprs']:>7}{k['scratch']:>9}{k['sgpr_spill'] + k['vgpr_spill']:>8}"
+                            f"{k['waves']:>12}{2 * 16 * mt * 256 + tables:>11}{sum(i.startswith('v_mfma') for i in k['insts']):>8}")
+    with open(os.path.join(REPO, "profiles", prof, "resource_usage.txt"), "w") as f:
+        f.write("\n".join(rows) + "\n")
+
+
+def compare(out, base):
+    bad = 0
+    for src in FAMILY:
+        new, old = kernels(out, src), kernels(base, src)
+        assert sorted(new) == sorted(old) and len(new) == 32, (src, len(new), len(old))
+        same = 0
+        for name in sorted(new, key=params):
+            n, o = new[name], old[name]
+            if n["insts"] == o["insts"]:
+                same += 1
+                continue
+            mf = [sum(i.startswith("v_mfma") for i in k["insts"]) for k in (n, o)]
+            keep = all(n[f] == o[f] for f in ("scratch", "sgpr_spill", "vgpr_spill", "waves", "agprs", "static_lds")) and mf[0] == mf[1]
+            bad += not keep
+            print(f"{src} DT,MT,SM,WV={params(name)}: streams differ ({len(o['insts'])} -> {len(n['insts'])} instructions); "
+                  f"VGPRs {o['vgprs']} -> {n['vgprs']}, SGPRs {o['sgprs']} -> {n['sgprs']}, AGPRs {o['agprs']} -> {n['agprs']}, "
+                  f"scratch {o['scratch']} -> {n['scratch']}, spills {o['sgpr_spill'] + o['vgpr_spill']} -> "
+                  f"{n['sgpr_spill'] + n['vgpr_spill']}, waves/SIMD {o['waves']} -> {n['waves']}, v_mfma {mf[1]} -> {mf[0]}"
+                  f"{'' if keep else '  <-- NOT KEPT'}")
+        print(f"{src}: {same} of {len(new)} instantiations have identical instruction streams")
+    return bad
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--csrc", default=os.path.join(PKG, "csrc"))
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--tables", action="store_true")
+    ap.add_argument("--against", default="")
+    ap.add_argument("--no-compile", action="store_true", help="--out already holds the .s and .log files")
+    args = ap.parse_args()
+    if not args.no_compile:
+        compile_all(args.csrc, args.out)
+    if args.tables:
+        for src in FAMILY:
+            write_table(args.out, src)
+    if args.against and compare(args.out, args.against):
+        sys.exit(1)
+
+
+if __name__ == "__main__":
+    main()
