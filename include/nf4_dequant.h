@@ -572,6 +572,49 @@ int nf4_gemm_bnb_mt_swiglu(const void* x, int64_t M, int64_t K,
                            int32_t act, void* h, int32_t out_dtype,
                            void* workspace, size_t workspace_bytes, const nf4_gemm_cfg* cfg, void* hip_stream);
 
+/* The first half of a mixture-of-experts block, `silu(w1(x)) * w3(x)` per (token, choice) pair,
+ * in bitsandbytes semantics: ONE launch for all experts, routed on the device -- the expert
+ * GEMM's anatomy (nf4_gemm_bnb_moe) with the SwiGLU launch's two-weight strips and rounding
+ * chain (nf4_gemm_bnb_mt_swiglu).  With int32 expert_ids[P] ON THE DEVICE, e = expert_ids[p] and
+ * rn = round-to-nearest-even to out_dtype (fp16 / bf16), for p in 0 .. P-1
+ *   g = rn(x[p / x_div] . Wg_e^T)   u = rn(x[p / x_div] . Wu_e^T)   what nf4_gemm_bnb_moe stores
+ *                                                                   for each stack
+ *   s = rn(g / (1.0f + expf(-g)))   h[p] = rn(s * u)                nf4_gemm_bnb_mt_swiglu's chain
+ * A pair whose id is outside [0, experts) gets a row of zero bits.  Every row of h ([P][I],
+ * dense) is stored by the launch; nothing else is written but the workspace.  The ids and the
+ * offsets are read when the kernel runs: no host copy, no synchronisation.  An expert without a
+ * pair costs no weight or statistics traffic.  Neither g nor u makes a trip through memory.
+ * `gate_up` points at TWO nf4_moe_experts in host memory, the gate stack (Mixtral's w1) then the
+ * up stack (w3); they are not interchangeable.  Each stack has its own base pointers, strides,
+ * statistics, offsets, code2 tables (code2_stride 0 = one table for its experts) and blocksize2;
+ * the two must agree in N (= I), K, experts and single (else NF4DQ_ERR_SHAPE).  `act` names the
+ * activation: NF4DQ_ACT_SILU (any other: NF4DQ_ERR_ARG).
+ * Rules: nf4_gemm_bnb_moe's with its codes and order, per stack -- 1 <= P <= NF4DQ_MOE_MAX_PAIRS,
+ * I % 64 == 0 and I >= 64, K % 128 == 0 and K >= 128, blocksize == 64, the strides long enough;
+ * else NF4DQ_ERR_SHAPE.  I > 2^18, more split-K tickets (experts * column tiles) than the
+ * workspace header holds, a workspace need of 2^32 bytes or more: NF4DQ_ERR_TOO_LARGE.  A null
+ * pointer (offset excepted), x / packed not 16-byte, h not 8-byte or expert_ids not 4-byte
+ * aligned, packed_stride % 16 != 0, a bad dtype, a block size that is no power of two, experts
+ * outside 1 .. NF4DQ_MOE_MAX_EXPERTS, x_div < 1 or a negative size: NF4DQ_ERR_ARG.  P == 0:
+ * NF4DQ_OK, nothing launched.
+ * cfg NULL = the library's choice from (P, experts, I, K, CU count) alone.  A cfg names kernel
+ * NF4DQ_GEMM_MOE_SWIGLU (0 = the same) with nf4_gemm_bnb_mt_swiglu's fields (waves 2 / 4: a
+ * workgroup owns 16 * waves columns of h; depth 1; ksplit 1 .. min(K / 128, 16); strips 2 or 0)
+ * and never falls back: an invalid one is NF4DQ_ERR_ARG.
+ * Workspace (nf4_gemm_bnb_moe_swiglu_workspace_bytes; 0 = none, one K slice): the ticket header,
+ * then per K slice the gate plane and the up plane of P * I floats indexed by pair
+ * ([ksplit][2][P][I]), all zero between calls, shareable with the other fused entries.  One
+ * ticket per (expert, column tile); the slice drawing the last one sums each plane in slice
+ * order over the expert's rows and applies the chain.  No workgroup waits for another, so the
+ * split-K error word is never set, and the result is a function of the inputs and the cfg alone.
+ * Asynchronous on `hip_stream`; one launch; allocates nothing; capturable in a graph. */
+#define NF4DQ_GEMM_MOE_SWIGLU 11
+size_t nf4_gemm_bnb_moe_swiglu_workspace_bytes(int64_t P, const void* gate_up, const nf4_gemm_cfg* cfg);
+int nf4_gemm_bnb_moe_swiglu(const void* x, const void* expert_ids, int64_t P, int32_t x_div,
+                            const void* gate_up /* nf4_moe_experts[2]: gate, up */, int32_t act,
+                            void* h, int32_t out_dtype,
+                            void* workspace, size_t workspace_bytes, const nf4_gemm_cfg* cfg, void* hip_stream);
+
 /* The split-K hand-off never hangs: a reducer that has polled a partner slice's
  * entries 2^16 times without seeing them gives up, reads them as NaN and sets a
  * sticky error word in the workspace header.  This call waits for `hip_stream`,

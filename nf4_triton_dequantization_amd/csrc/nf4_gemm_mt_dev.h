@@ -4,7 +4,9 @@
 // policies.  nf4_gemm_moe.hip (one expert's listed rows) shares the ring entry, the rotation, the
 // decode, the MFMA call, the split-K hand-off and the reducer, and keeps its own chunk loop: its
 // row-tile guards are run-time, and built from the shared loop it did not keep the registers,
-// spills and speed it had (profiles/gemm_mt_family/README.md).
+// spills and speed it had (profiles/gemm_mt_family/README.md).  nf4_gemm_moe_swiglu.hip (one
+// expert's listed rows, gate and up with the SwiGLU chain) is that loop over MtStrips<2>, its own
+// copy for the same reason, with the hand-off, the reducer and the chain from here.
 //
 // y[M][N] = x[M][K] . W[N][K]^T with W the 16-bit weights nf4_dequant_bnb writes, bit for
 // bit.  The families of nf4_gemm_dev.h hold x whole (LDS or registers) and at most two row
@@ -60,8 +62,9 @@
 //    staged, which row of x a staged row is loaded from and which row of y it is stored to;
 //  * strips (MtStrips<1>, MtStrips<2>): what a wave's two strips are -- two column strips
 //    of one weight, or the same 16 rows of two weights, each with its own statistics;
-//  * output (MtSumOut here, the SwiGLU chain in nf4_gemm_mt_swiglu.hip): how many fp32 planes a
-//    slice stores and what becomes of the two strips' sums.
+//  * output (MtSumOut; SgOut, the SwiGLU chain of nf4_gemm_mt_swiglu.hip and
+//    nf4_gemm_moe_swiglu.hip): how many fp32 planes a slice stores and what becomes of the two
+//    strips' sums.
 #pragma once
 
 #include "nf4_gemm_launch.h"
@@ -168,6 +171,39 @@ struct MtSumOut {
     }
     static __device__ __forceinline__ u32x2 pack4(const f32x4 (&s)[1]) {
         return u32x2{pack2<DT>(s[0].x, s[0].y), pack2<DT>(s[0].z, s[0].w)};
+    }
+};
+
+// RNE to the 16-bit type and back.  (opaque: the backend must not fold the rounding into the
+// operation before it -- v_fma_mix rounds once where the chain rounds twice)
+template <int DT>
+__device__ __forceinline__ float rne16(float v) {
+    if constexpr (DT == NF4DQ_BF16) return (float)(__bf16)opaque(v);
+    else return (float)(_Float16)opaque(v);
+}
+
+// The chain behind the two 16-bit GEMM results: fp32 silu with IEEE division, one rounding,
+// the (exact) fp32 product, one rounding.  Returns h widened to fp32.
+template <int DT>
+__device__ __forceinline__ float swiglu16(float acc_g, float acc_u) {
+    const float g = rne16<DT>(acc_g), u = rne16<DT>(acc_u);
+    const float s = rne16<DT>(g / (1.0f + expf(-g)));
+    return rne16<DT>(s * u);
+}
+
+// Output policy, SwiGLU: the strips are g and u of ONE column of h; two fp32 planes per slice
+// (g, u), the chain behind the two sums.
+template <int DT>
+struct SgOut {
+    static constexpr uint32_t kPlanes = 2;
+    static __device__ __forceinline__ uint32_t slab_at(int nt, uint32_t plane) { return (uint32_t)nt * plane; }
+    static __device__ __forceinline__ void store(void* h, uint32_t at, uint32_t nl, float g, float u) {
+        store_y<DT>(h, at + nl, swiglu16<DT>(g, u));  // exact: a 16-bit value
+    }
+    static __device__ __forceinline__ u32x2 pack4(const f32x4 (&s)[2]) {
+        const f32x4 g = s[0], u = s[1];
+        return u32x2{pack2<DT>(swiglu16<DT>(g.x, u.x), swiglu16<DT>(g.y, u.y)),
+                     pack2<DT>(swiglu16<DT>(g.z, u.z), swiglu16<DT>(g.w, u.w))};
     }
 };
 

@@ -36,38 +36,8 @@ struct SgArgs {
     uint32_t sh2[2];           // log2(blocksize2)
 };
 
-// RNE to the 16-bit type and back.  (opaque: the backend must not fold the rounding into the
-// operation before it -- v_fma_mix rounds once where the chain rounds twice)
-template <int DT>
-__device__ __forceinline__ float rne16(float v) {
-    if constexpr (DT == NF4DQ_BF16) return (float)(__bf16)opaque(v);
-    else return (float)(_Float16)opaque(v);
-}
-
-// The chain behind the two 16-bit GEMM results: fp32 silu with IEEE division, one rounding,
-// the (exact) fp32 product, one rounding.  Returns h widened to fp32.
-template <int DT>
-__device__ __forceinline__ float swiglu16(float acc_g, float acc_u) {
-    const float g = rne16<DT>(acc_g), u = rne16<DT>(acc_u);
-    const float s = rne16<DT>(g / (1.0f + expf(-g)));
-    return rne16<DT>(s * u);
-}
-
-// Output policy: two fp32 planes per slice (g, u), the chain behind the two sums.
-template <int DT>
-struct SgOut {
-    static constexpr uint32_t kPlanes = 2;
-    static __device__ __forceinline__ uint32_t slab_at(int nt, uint32_t plane) { return (uint32_t)nt * plane; }
-    static __device__ __forceinline__ void store(void* h, uint32_t at, uint32_t nl, float g, float u) {
-        store_y<DT>(h, at + nl, swiglu16<DT>(g, u));  // exact: a 16-bit value
-    }
-    static __device__ __forceinline__ u32x2 pack4(const f32x4 (&s)[2]) {
-        const f32x4 g = s[0], u = s[1];
-        return u32x2{pack2<DT>(swiglu16<DT>(g.x, u.x), swiglu16<DT>(g.y, u.y)),
-                     pack2<DT>(swiglu16<DT>(g.z, u.z), swiglu16<DT>(g.w, u.w))};
-    }
-};
-
+// (the chain -- rne16, swiglu16 -- and the two-plane output policy SgOut are nf4_gemm_mt_dev.h's:
+// the expert SwiGLU launch, nf4_gemm_moe_swiglu.hip, uses the same ones)
 template <int DT, int MT, int SM, int WV>
 __global__ __launch_bounds__(64 * WV) void nf4_gemm_mt_swiglu_kernel(const SgArgs A) {
     extern __shared__ __attribute__((aligned(16))) char smem[];  // [x buffer 0][x buffer 1][code2 gate][code2 up][codes][flag]

@@ -932,6 +932,63 @@ def _moe_fallback(x3: torch.Tensor, experts, ids: torch.Tensor, out: torch.Tenso
     return out
 
 
+def _moe_args(name: str, x: torch.Tensor, experts, expert_ids: torch.Tensor):
+    """The argument checks of the expert entries: ``(T, k, x_div, x as [T, 1 or k, K])``."""
+    K = int(experts.in_features)
+    dev = experts.weight.data.device
+    if expert_ids.dim() != 2 or expert_ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name}: expert_ids must be int32 or int64 [T, k], got {expert_ids.dtype} "
+                         f"{tuple(expert_ids.shape)}")
+    T, k = int(expert_ids.shape[0]), int(expert_ids.shape[1])
+    if x.dim() == 2 and tuple(x.shape) == (T, K):
+        x_div, x3 = k, x.unsqueeze(1)
+    elif x.dim() == 3 and tuple(x.shape) == (T, k, K):
+        x_div, x3 = 1, x
+    else:
+        raise RuntimeError(f"{name}: x must be [{T}, {K}] or [{T}, {k}, {K}], got {tuple(x.shape)}")
+    if x.device != dev or expert_ids.device != dev:
+        raise RuntimeError(f"Expected all tensors to be on the same device, but found at least two devices, "
+                           f"{dev} and {x.device if x.device != dev else expert_ids.device}!")
+    return T, k, x_div, x3
+
+
+def _moe_fusable(x: torch.Tensor, experts, P: int) -> bool:
+    """The fused-route conditions of the expert entries on one ``Experts4bit`` (nf4_moe_linear_bnb's docstring)."""
+    N, K, E = int(experts.out_features), int(experts.in_features), int(experts.num_experts)
+    q = experts.weight.data
+    return (q.device.type == "cuda" and experts.dtype in (torch.float16, torch.bfloat16) and 1 <= P <= _lib.MOE_MAX_PAIRS
+            and N % 64 == 0 and N >= 64 and K % 128 == 0 and K >= 128 and 1 <= E <= _lib.MOE_MAX_EXPERTS
+            and int(experts.blocksize) == 64 and q.dtype == torch.uint8 and q.is_contiguous()
+            and q.data_ptr() % 16 == 0 and (N * K // 2) % 16 == 0
+            and not (torch.is_grad_enabled() and x.requires_grad))
+
+
+def _moe_operands(x: torch.Tensor, expert_ids: torch.Tensor, dtype: torch.dtype):
+    """x and the ids as the expert entries read them: the dtype, contiguous, x 16-byte aligned, int32 ids."""
+    xc = x if x.dtype == dtype else x.to(dtype)
+    xc = xc.contiguous()
+    if xc.data_ptr() % 16:
+        xc = xc.clone()  # a view at an odd offset: the entry loads 16 bytes at a time
+    ids = expert_ids if expert_ids.dtype == torch.int32 else expert_ids.to(torch.int32)
+    return xc, ids.contiguous()
+
+
+def _moe_desc(experts) -> "_lib.MoeExperts":
+    """The nf4_moe_experts descriptor of an ``Experts4bit``: base pointers and strides."""
+    N, K, E = int(experts.out_features), int(experts.in_features), int(experts.num_experts)
+    q = experts.weight.data
+    dev = q.device
+    _on_device(dev, experts.absmax)
+    am = experts.absmax
+    if bool(experts.nested):
+        _on_device(dev, experts.absmax2, experts.code2, experts.offset)
+        return _lib.MoeExperts(q.data_ptr(), q.stride(0), am.data_ptr(), am.stride(0), experts.code2.data_ptr(), 0,
+                               experts.absmax2.data_ptr(), experts.absmax2.stride(0), experts.offset.data_ptr(),
+                               N, K, E, 0, 64, int(experts.blocksize2))
+    return _lib.MoeExperts(q.data_ptr(), q.stride(0), None, 0, None, 0, am.data_ptr(), am.stride(0), None,
+                           N, K, E, 1, 64, 0)
+
+
 def nf4_moe_linear_bnb(x: torch.Tensor, experts, expert_ids: torch.Tensor,
                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One projection of a mixture-of-experts block for all experts, in bitsandbytes semantics:
@@ -956,23 +1013,10 @@ def nf4_moe_linear_bnb(x: torch.Tensor, experts, expert_ids: torch.Tensor,
     follows it to ``x``.  Both routes use the same weights and fp32 accumulation; the summation
     order differs, so the last bit of ``y`` may.
     """
-    N, K, E = int(experts.out_features), int(experts.in_features), int(experts.num_experts)
+    N, K = int(experts.out_features), int(experts.in_features)
     dtype = experts.dtype
-    q = experts.weight.data
-    dev = q.device
-    if expert_ids.dim() != 2 or expert_ids.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"nf4_moe_linear_bnb: expert_ids must be int32 or int64 [T, k], got {expert_ids.dtype} "
-                         f"{tuple(expert_ids.shape)}")
-    T, k = int(expert_ids.shape[0]), int(expert_ids.shape[1])
-    if x.dim() == 2 and tuple(x.shape) == (T, K):
-        x_div, x3 = k, x.unsqueeze(1)
-    elif x.dim() == 3 and tuple(x.shape) == (T, k, K):
-        x_div, x3 = 1, x
-    else:
-        raise RuntimeError(f"nf4_moe_linear_bnb: x must be [{T}, {K}] or [{T}, {k}, {K}], got {tuple(x.shape)}")
-    if x.device != dev or expert_ids.device != dev:
-        raise RuntimeError(f"Expected all tensors to be on the same device, but found at least two devices, "
-                           f"{dev} and {x.device if x.device != dev else expert_ids.device}!")
+    dev = experts.weight.data.device
+    T, k, x_div, x3 = _moe_args("nf4_moe_linear_bnb", x, experts, expert_ids)
     if out is None:
         out = torch.empty((T, k, N), dtype=dtype, device=dev)
     elif tuple(out.shape) != (T, k, N) or out.dtype != dtype or out.device != dev or not out.is_contiguous():
@@ -980,30 +1024,10 @@ def nf4_moe_linear_bnb(x: torch.Tensor, experts, expert_ids: torch.Tensor,
     P = T * k
     if P == 0:
         return out
-    fused = (dev.type == "cuda" and dtype in (torch.float16, torch.bfloat16) and 1 <= P <= _lib.MOE_MAX_PAIRS
-             and N % 64 == 0 and N >= 64 and K % 128 == 0 and K >= 128 and 1 <= E <= _lib.MOE_MAX_EXPERTS
-             and int(experts.blocksize) == 64 and q.dtype == torch.uint8 and q.is_contiguous()
-             and q.data_ptr() % 16 == 0 and (N * K // 2) % 16 == 0
-             and not (torch.is_grad_enabled() and x.requires_grad))
-    if not fused:
+    if not _moe_fusable(x, experts, P):
         return _moe_fallback(x3, experts, expert_ids, out)
-    xc = x if x.dtype == dtype else x.to(dtype)
-    xc = xc.contiguous()
-    if xc.data_ptr() % 16:
-        xc = xc.clone()  # a view at an odd offset: the entry loads 16 bytes at a time
-    ids = expert_ids if expert_ids.dtype == torch.int32 else expert_ids.to(torch.int32)
-    ids = ids.contiguous()
-    nested = bool(experts.nested)
-    _on_device(dev, experts.absmax)
-    am = experts.absmax
-    if nested:
-        _on_device(dev, experts.absmax2, experts.code2, experts.offset)
-        desc = _lib.MoeExperts(q.data_ptr(), q.stride(0), am.data_ptr(), am.stride(0), experts.code2.data_ptr(), 0,
-                               experts.absmax2.data_ptr(), experts.absmax2.stride(0), experts.offset.data_ptr(),
-                               N, K, E, 0, 64, int(experts.blocksize2))
-    else:
-        desc = _lib.MoeExperts(q.data_ptr(), q.stride(0), None, 0, None, 0, am.data_ptr(), am.stride(0), None,
-                               N, K, E, 1, 64, 0)
+    xc, ids = _moe_operands(x, expert_ids, dtype)
+    desc = _moe_desc(experts)
     L = _lib.lib()
     dp = ctypes.cast(ctypes.pointer(desc), ctypes.c_void_p)
     with torch.cuda.device(dev):
@@ -1138,3 +1162,95 @@ def nf4_mlp_bnb(x: torch.Tensor, gate_proj, up_proj, down_proj) -> torch.Tensor:
     """``down_proj(F.silu(gate_proj(x)) * up_proj(x))`` for ``Linear4bit`` weights in bitsandbytes
     semantics: ``nf4_linear_bnb(nf4_swiglu_bnb(x, gate_proj, up_proj), down_proj)`` and nothing else."""
     return nf4_linear_bnb(nf4_swiglu_bnb(x, gate_proj, up_proj), down_proj)
+
+
+# (token, choice) pairs at which nf4_moe_swiglu_bnb takes the fused launch (nf4_gemm_bnb_moe_swiglu):
+# the span of the T * k of {2, 8, 32, 128} at which it measured faster than what a caller did
+# before -- two nf4_moe_linear_bnb launches, then F.silu(g) * u: four launches -- at Mixtral-8x7B's
+# w1 / w3 (8 experts, top-2, 14336x4096, bf16, graph replay, weights from HBM) by more than the
+# run-to-run spread of the rounds (profiles/gemm_moe_swiglu/, README, DESIGN section 4b).  It did at
+# all four: 56 against 84 us at 2 pairs (1.49x), 140 / 174 at 8 (1.25x), 185 / 212 at 32 (1.15x),
+# 357 / 410 at 128 (1.15x), the slower of two runs of the fused launch against the faster of two
+# of the composite, where a route's rounds spread over 1 - 6 us.  One pair was not measured and is
+# not routed.  An empty range (MIN above MAX) would mean the fused launch is reached through the C
+# entry alone.
+MOE_SWIGLU_ROUTED_MIN_P = 2
+MOE_SWIGLU_ROUTED_MAX_P = 128
+
+
+def nf4_moe_swiglu_bnb(x: torch.Tensor, gate_experts, up_experts, expert_ids: torch.Tensor,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The first half of a mixture-of-experts block, Mixtral's ``F.silu(w1(x)) * w3(x)`` per
+    (token, choice) pair, in bitsandbytes semantics:
+    ``F.silu(nf4_moe_linear_bnb(x, gate_experts, ids)) * nf4_moe_linear_bnb(x, up_experts, ids)``.
+
+    ``gate_experts`` and ``up_experts`` are ``Experts4bit`` of one shape ``[I, K]``, one expert
+    count, one dtype and both with nested statistics or both with fp32 ``absmax`` (else
+    ``ValueError``); ``expert_ids`` is ``[T, k]``, int32 or int64; ``x`` is ``[T, K]`` or
+    ``[T, k, K]`` -- all as in ``nf4_moe_linear_bnb``, with its checks and errors.  Returns
+    ``[T, k, I]`` in the experts' dtype (written into ``out`` when given: contiguous, that shape
+    and dtype).  A pair whose id is outside ``0..E-1`` gets a row of zeros.
+
+    The fused route is ONE launch (``nf4_gemm_bnb_moe_swiglu``) plus at most a cast of the ids:
+    the ids are balloted and x gathered and staged once for both weights, neither ``g`` nor ``u``
+    makes a trip through memory, the ids and the offsets are read on the device, nothing
+    synchronises with the host and ``torch.cuda.graph`` captures the call.  It is taken under
+    ``nf4_moe_linear_bnb``'s fused-route conditions on both stacks and
+    ``MOE_SWIGLU_ROUTED_MIN_P <= T*k <= MOE_SWIGLU_ROUTED_MAX_P``.  Everything else -- other pair
+    counts, more than ``MOE_MAX_PAIRS`` pairs, CPU tensors, a gradient being recorded for ``x``
+    -- is the expression above, which has the same definition and which autograd follows; the
+    GEMMs' summation order may differ between the routes, so the last bit of ``g`` and ``u`` may.
+    """
+    I, K, E = int(gate_experts.out_features), int(gate_experts.in_features), int(gate_experts.num_experts)
+    if ((int(up_experts.out_features), int(up_experts.in_features), int(up_experts.num_experts)) != (I, K, E)
+            or up_experts.dtype != gate_experts.dtype or bool(up_experts.nested) != bool(gate_experts.nested)):
+        raise ValueError(f"nf4_moe_swiglu_bnb: gate_experts is {E} x [{I}, {K}] {gate_experts.dtype} "
+                         f"{'nested' if gate_experts.nested else 'fp32 absmax'}, up_experts "
+                         f"{int(up_experts.num_experts)} x [{int(up_experts.out_features)}, {int(up_experts.in_features)}] "
+                         f"{up_experts.dtype} {'nested' if up_experts.nested else 'fp32 absmax'}")
+    dtype = gate_experts.dtype
+    dev = gate_experts.weight.data.device
+    T, k, x_div, _ = _moe_args("nf4_moe_swiglu_bnb", x, gate_experts, expert_ids)
+    if up_experts.weight.data.device != dev:
+        raise RuntimeError(f"Expected all tensors to be on the same device, but found at least two devices, "
+                           f"{dev} and {up_experts.weight.data.device}!")
+    if out is not None and (tuple(out.shape) != (T, k, I) or out.dtype != dtype or out.device != dev
+                            or not out.is_contiguous()):
+        raise ValueError(f"nf4_moe_swiglu_bnb: out must be a contiguous {dtype} [{T}, {k}, {I}] tensor on {dev}")
+    P = T * k
+    fused = (MOE_SWIGLU_ROUTED_MIN_P <= P <= MOE_SWIGLU_ROUTED_MAX_P and _moe_fusable(x, gate_experts, P)
+             and _moe_fusable(x, up_experts, P))
+    if not fused:
+        h = torch.nn.functional.silu(nf4_moe_linear_bnb(x, gate_experts, expert_ids)) \
+            * nf4_moe_linear_bnb(x, up_experts, expert_ids)
+        if out is None:
+            return h
+        out.copy_(h)
+        return out
+    if out is None:
+        out = torch.empty((T, k, I), dtype=dtype, device=dev)
+    xc, ids = _moe_operands(x, expert_ids, dtype)
+    descs = (_lib.MoeExperts * 2)(_moe_desc(gate_experts), _moe_desc(up_experts))
+    L = _lib.lib()
+    dp = ctypes.cast(descs, ctypes.c_void_p)
+    with torch.cuda.device(dev):
+        ws_bytes = L.nf4_gemm_bnb_moe_swiglu_workspace_bytes(P, dp, None)
+        ws = _gemm_workspace(dev, ws_bytes) if ws_bytes else None
+        rc = L.nf4_gemm_bnb_moe_swiglu(xc.data_ptr(), ids.data_ptr(), P, x_div, dp, _lib.ACT_SILU, out.data_ptr(),
+                                       _dtype_code(dtype), ws.data_ptr() if ws is not None else None, ws_bytes, None,
+                                       torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "nf4 fused moe swiglu gemm")
+    return out
+
+
+def nf4_moe_mlp_bnb(x: torch.Tensor, w1, w3, w2, expert_ids: torch.Tensor,
+                    routing_weights: torch.Tensor) -> torch.Tensor:
+    """A whole mixture-of-experts MLP block (Mixtral's) for ``Experts4bit`` stacks in bitsandbytes
+    semantics: ``sum_j routing_weights[t, j] * w2_e(F.silu(w1_e(x[t])) * w3_e(x[t]))`` with
+    ``e = expert_ids[t, j]``.  ``x`` is ``[T, H]``, ``expert_ids`` and ``routing_weights``
+    ``[T, k]`` (the weights in any float dtype); returns ``[T, H]``.  It has no logic of its own:
+    ``nf4_moe_swiglu_bnb``, ``nf4_moe_linear_bnb`` and the weighted combine in torch, so it is
+    capturable in a graph whenever its parts are, and autograd follows it to ``x``."""
+    h = nf4_moe_swiglu_bnb(x, w1, w3, expert_ids)
+    d = nf4_moe_linear_bnb(h, w2, expert_ids)
+    return (d * routing_weights.to(d.dtype).unsqueeze(-1)).sum(dim=1)

@@ -1,11 +1,13 @@
 """Device assembly and resource usage of the row-tiled GEMM family (nf4_gemm_mt.hip,
-nf4_gemm_mt_swiglu.hip, nf4_gemm_moe.hip), and one tree's kernels against another's.
+nf4_gemm_mt_swiglu.hip, nf4_gemm_moe.hip, nf4_gemm_moe_swiglu.hip), and one tree's kernels against
+another's.
 
     python tools/gemm_mt_family_asm.py --out DIR [--csrc DIR] [--tables] [--against DIR]
 
-Compiles the three sources of ``--csrc`` (default: this tree's) to device assembly with the
+Compiles the family's sources of ``--csrc`` (default: this tree's; one that tree lacks is left out)
+to device assembly with the
 Makefile's flags (``--cuda-device-only -S -Rpass-analysis=kernel-resource-usage``, without
--Werror) into ``--out``.  ``--tables`` rewrites profiles/gemm_{mt,mt_swiglu,moe}/resource_usage.txt
+-Werror) into ``--out``.  ``--tables`` rewrites profiles/gemm_{mt,mt_swiglu,moe,moe_swiglu}/resource_usage.txt
 from the compiler's remarks.  ``--against DIR`` (an ``--out`` of another tree, e.g. the parent
 commit's sources) compares kernel by kernel: the instruction streams after dropping comments and
 directives and renumbering labels, and where they differ scratch, spills, waves per SIMD,
@@ -39,7 +41,8 @@ FLAGS = makefile_flags()
 # source -> (profiles directory, kernel, bytes of tables behind the x buffers: the plan headers' k*TableBytes)
 FAMILY = {"nf4_gemm_mt": ("gemm_mt", "nf4_gemm_mt_kernel", 1104),
           "nf4_gemm_mt_swiglu": ("gemm_mt_swiglu", "nf4_gemm_mt_swiglu_kernel", 2128),
-          "nf4_gemm_moe": ("gemm_moe", "nf4_gemm_moe_kernel", 2128)}
+          "nf4_gemm_moe": ("gemm_moe", "nf4_gemm_moe_kernel", 2128),
+          "nf4_gemm_moe_swiglu": ("gemm_moe_swiglu", "nf4_gemm_moe_swiglu_kernel", 3152)}
 FIELDS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch",
           "Occupancy [waves/SIMD]": "waves", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill",
           "LDS Size [bytes/block]": "static_lds"}
@@ -49,6 +52,8 @@ def compile_all(csrc, out):
     os.makedirs(out, exist_ok=True)
     procs = []
     for src in FAMILY:
+        if not os.path.exists(os.path.join(csrc, src + ".hip")):
+            continue
         log = open(os.path.join(out, src + ".log"), "w")
         cmd = [HIPCC, *FLAGS, "-I", os.path.join(REPO, "include"), "-o", os.path.join(out, src + ".s"),
                os.path.join(csrc, src + ".hip")]
@@ -114,6 +119,9 @@ def write_table(out, src):
 def compare(out, base):
     bad = 0
     for src in FAMILY:
+        if not os.path.exists(os.path.join(base, src + ".s")):
+            print(f"{src}: not in the other tree")
+            continue
         new, old = kernels(out, src), kernels(base, src)
         assert sorted(new) == sorted(old) and len(new) == 32, (src, len(new), len(old))
         same = 0
@@ -146,7 +154,8 @@ def main():
         compile_all(args.csrc, args.out)
     if args.tables:
         for src in FAMILY:
-            write_table(args.out, src)
+            if os.path.exists(os.path.join(args.out, src + ".s")):
+                write_table(args.out, src)
     if args.against and compare(args.out, args.against):
         sys.exit(1)
 
