@@ -615,6 +615,46 @@ int nf4_gemm_bnb_moe_swiglu(const void* x, const void* expert_ids, int64_t P, in
                             void* h, int32_t out_dtype,
                             void* workspace, size_t workspace_bytes, const nf4_gemm_cfg* cfg, void* hip_stream);
 
+/* The second half of a mixture-of-experts block, the down projection (Mixtral's w2) WITH the
+ * routed weighted sum, in bitsandbytes semantics: ONE launch for all experts, routed on the
+ * device -- the expert GEMM (nf4_gemm_bnb_moe) with the combine of a token's `topk` pairs behind
+ * it.  With int32 expert_ids[P] and routing_weights[P] ON THE DEVICE, e = expert_ids[p] and
+ * rn = round-to-nearest-even to out_dtype (fp16 / bf16), for t in 0 .. P / topk - 1
+ *   d[p] = rn(x[p / x_div] . W_e^T)                   exactly what nf4_gemm_bnb_moe stores for the
+ *                                                     pair under the same (waves, ksplit);
+ *                                                     +0 for an id outside [0, experts)
+ *   y[t] = rn(sum_j rn(d[t topk + j] * rn(rw[t topk + j])))     j = 0 .. topk-1
+ * The product is formed in fp32 (exact for two 16-bit values) and rounded once; the sum is fp32,
+ * starts from +0.0f and adds j = 0, 1, .. in that order, rounded once -- the rounding chain of
+ * `(d * rw.to(dtype).unsqueeze(-1)).sum(dim=1)` on 16-bit tensors with the order spelled out, so
+ * -0 + -0 gives +0 and a NaN weight gives NaN also for an invalid id.  y is [P / topk][N], dense;
+ * every row is stored by the launch; the [P][N] products never leave the workspace.
+ * `routing_weights` is fp32 (rw_dtype NF4DQ_F32: rounded to out_dtype on the device, as a cast
+ * does) or out_dtype (rw_dtype == out_dtype); 4-byte or 2-byte aligned.  Any other rw_dtype,
+ * topk < 1, topk > P or P % topk != 0: NF4DQ_ERR_ARG.
+ * Every other rule, code and their order are nf4_gemm_bnb_moe's: 1 <= P <= NF4DQ_MOE_MAX_PAIRS,
+ * N % 64 == 0, K % 128 == 0, blocksize == 64, the alignments (y 8-byte), the size limits.
+ * P == 0: NF4DQ_OK, nothing launched.
+ * cfg NULL = the library's choice, nf4_gemm_bnb_moe's for the same (P, experts, N, K, CU count).
+ * A cfg names kernel NF4DQ_GEMM_MOE_DOWN (0 = the same) with nf4_gemm_bnb_moe's fields and never
+ * falls back: an invalid one is NF4DQ_ERR_ARG.
+ * Workspace (nf4_gemm_bnb_moe_down_workspace_bytes; never 0 for a valid call): the ticket header
+ * -- experts * column tiles tickets of the K slices, then one ticket per column tile for the
+ * combine; more than the header holds: NF4DQ_ERR_TOO_LARGE --, then ksplit slabs of P * N floats
+ * when ksplit > 1, then P * N 16-bit products.  Header and slabs are zero between calls, as for
+ * the other fused entries; the products are don't-care (every one read was written by the same
+ * call).  Per column tile each expert arrives once, after its rows are stored (an expert without
+ * a pair at once, with no weight or statistics traffic); the last arrival combines the tile.  No
+ * workgroup waits for another, so the split-K error word is never set, and the result is a
+ * function of the inputs and the cfg alone.
+ * Asynchronous on `hip_stream`; one launch; allocates nothing; capturable in a graph. */
+#define NF4DQ_GEMM_MOE_DOWN 12
+size_t nf4_gemm_bnb_moe_down_workspace_bytes(int64_t P, const void* experts, const nf4_gemm_cfg* cfg);
+int nf4_gemm_bnb_moe_down(const void* x, const void* expert_ids, int64_t P, int32_t x_div, int32_t topk,
+                          const void* routing_weights, int32_t rw_dtype, const void* experts, void* y,
+                          int32_t out_dtype, void* workspace, size_t workspace_bytes,
+                          const nf4_gemm_cfg* cfg, void* hip_stream);
+
 /* The split-K hand-off never hangs: a reducer that has polled a partner slice's
  * entries 2^16 times without seeing them gives up, reads them as NaN and sets a
  * sticky error word in the workspace header.  This call waits for `hip_stream`,

@@ -81,6 +81,7 @@ GEMM_MT = 8  # the row-tiled family (nf4_gemm_bnb_mt*: up to 128 rows); its own 
 GEMM_MOE = 9  # the expert GEMM of a mixture-of-experts block (nf4_gemm_bnb_moe); its own entry only
 GEMM_MT_SWIGLU = 10  # the fused gate/up SwiGLU launch (nf4_gemm_bnb_mt_swiglu); its own entry only
 GEMM_MOE_SWIGLU = 11  # the fused expert SwiGLU launch (nf4_gemm_bnb_moe_swiglu); its own entry only
+GEMM_MOE_DOWN = 12  # the fused expert down projection with the routed sum (nf4_gemm_bnb_moe_down); its own entry only
 ACT_SILU = 0  # NF4DQ_ACT_SILU: the activation of nf4_gemm_bnb_mt_swiglu and nf4_gemm_bnb_moe_swiglu
 MOE_MAX_PAIRS = 128    # NF4DQ_MOE_MAX_PAIRS: (token, choice) pairs of one nf4_gemm_bnb_moe launch
 MOE_MAX_EXPERTS = 256  # NF4DQ_MOE_MAX_EXPERTS
@@ -182,6 +183,10 @@ SIGNATURES = {
     "nf4_gemm_bnb_moe_swiglu_workspace_bytes": (ctypes.c_size_t, [_I64, _P, ctypes.POINTER(GemmCfg)]),
     "nf4_gemm_bnb_moe_swiglu": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _I32, _P, _I32, _P, ctypes.c_size_t,
                                                ctypes.POINTER(GemmCfg), _P]),
+    # `experts`: const void* in the header, pointing at ONE MoeExperts; ids and routing weights on the device
+    "nf4_gemm_bnb_moe_down_workspace_bytes": (ctypes.c_size_t, [_I64, _P, ctypes.POINTER(GemmCfg)]),
+    "nf4_gemm_bnb_moe_down": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _I32, _P, _P, _I32, _P, ctypes.c_size_t,
+                                             ctypes.POINTER(GemmCfg), _P]),
     "nf4_gemm_check_workspace": (ctypes.c_int, [_P, ctypes.c_size_t, _P]),
     "nf4_strerror": (ctypes.c_char_p, [ctypes.c_int]),
     "nf4_version": (ctypes.c_char_p, []),

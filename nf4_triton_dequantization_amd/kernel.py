@@ -540,6 +540,23 @@ def _gemm_workspace(device: torch.device, nbytes: int) -> torch.Tensor:
     return ws
 
 
+# nf4_moe_down_bnb's workspaces, apart from the shared ones: the launch leaves its 16-bit products
+# behind the slabs, where another entry's larger slabs would expect zeros.  Their tickets and
+# slabs are 0 between calls like the shared ones'; no workgroup of that launch waits for another,
+# so their error word is never set and check_gemm_workspaces() has nothing to read in them.
+_MOE_DOWN_WS = {}
+
+
+def _moe_down_workspace(device: torch.device, nbytes: int) -> torch.Tensor:
+    """``_gemm_workspace`` for ``nf4_moe_down_bnb`` alone: one per (device, stream), grown on demand."""
+    stream = torch.cuda.current_stream(device)
+    key = (device.index, stream.cuda_stream)
+    ent = _MOE_DOWN_WS.get(key)
+    if ent is None or ent[0].numel() < nbytes:
+        ent = _MOE_DOWN_WS[key] = (torch.zeros(nbytes, dtype=torch.uint8, device=device), stream)
+    return ent[0]
+
+
 def release_gemm_workspaces() -> None:
     """Forget every cached split-K workspace: for callers that destroy their own external
     streams.  Each workspace's sticky error word is read first (which also waits for its
@@ -550,6 +567,7 @@ def release_gemm_workspaces() -> None:
         check_gemm_workspaces()
     finally:
         _GEMM_WS.clear()
+        _MOE_DOWN_WS.clear()
 
 
 def check_gemm_workspaces() -> None:
@@ -1243,14 +1261,125 @@ def nf4_moe_swiglu_bnb(x: torch.Tensor, gate_experts, up_experts, expert_ids: to
     return out
 
 
+# (token, choice) pairs at which nf4_moe_down_bnb takes the fused launch (nf4_gemm_bnb_moe_down):
+# those of the measured T * k in {2, 8, 32, 128} at which it was faster than the composite it
+# replaces -- nf4_moe_linear_bnb, then the cast, the product and the sum in torch: four launches --
+# at Mixtral-8x7B's w2 (8 experts, top-2, 4096x14336, bf16, graph replay, weights from HBM) by more
+# than the run-to-run spread of the rounds (profiles/gemm_moe_down/, README).
+# There is none: 65 against 51 us at 2 pairs (0.78x), 111 / 112 at 8 (1.01x, inside the rounds'
+# spread of up to 5 us), 123 / 120 at 32 (0.97x), 218 / 215 at 128 (0.98x) -- the slower of two
+# runs of the fused launch against the faster of two of the composite.  In a replayed graph the
+# three elementwise launches cost about 6 us; the second ticket and the combine behind the last
+# reducer cost as much or more.  So the range is EMPTY (MIN above MAX): the fused launch is
+# reached through the C entry, or by a caller who sets these constants.
+MOE_DOWN_ROUTED_MIN_P = 1
+MOE_DOWN_ROUTED_MAX_P = 0
+
+# The largest top-k at which nf4_moe_mlp_bnb calls nf4_moe_down_bnb in place of its last two
+# lines: with two fp32 terms the sum is order-free, so the result is bit for bit the torch
+# expression's; for k > 2 torch's reduction order is not promised and the last bit could move.
+MOE_DOWN_MLP_MAX_K = 2
+
+
+def _moe_down_chain(d: torch.Tensor, rw: torch.Tensor) -> torch.Tensor:
+    """The combine as the fused launch defines it, on tensors: the products in d's dtype, then the
+    fp32 sum from +0 in the order j = 0 .. k-1, rounded once.  Up to two terms ``sum`` is that sum
+    whatever its order (it accumulates 16-bit inputs in fp32 from +0 and rounds once); beyond, the
+    order is spelled out."""
+    prod = d * rw.to(d.dtype).unsqueeze(-1)
+    if d.shape[1] <= 2:
+        return prod.sum(dim=1)
+    acc = torch.zeros((d.shape[0], d.shape[2]), dtype=torch.float32, device=d.device)
+    for j in range(d.shape[1]):
+        acc = acc + prod[:, j].float()
+    return acc.to(d.dtype)
+
+
+def nf4_moe_down_bnb(h: torch.Tensor, experts, expert_ids: torch.Tensor, routing_weights: torch.Tensor,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The second half of a mixture-of-experts block, Mixtral's ``w2`` with the routed weighted
+    sum, in bitsandbytes semantics: ``y[t] = sum_j routing_weights[t, j] * (h[t, j] @ W_e.t())``
+    with ``e = expert_ids[t, j]``.
+
+    ``experts``, ``expert_ids`` ``[T, k]`` and ``h`` (``[T, k, K]``, or ``[T, K]`` shared by the
+    token's choices) are as in ``nf4_moe_linear_bnb``, with its checks and errors;
+    ``routing_weights`` is ``[T, k]`` in any float dtype on the same device.  Returns ``[T, N]``
+    in the experts' dtype (written into ``out`` when given: contiguous, that shape and dtype).
+
+    The result is this chain, with ``rn`` the rounding to the experts' dtype: ``d =
+    nf4_moe_linear_bnb(h, experts, expert_ids)`` (rows of zeros for ids outside ``0..E-1``),
+    ``p[t, j] = rn(d[t, j] * rn(routing_weights[t, j]))`` (the fp32 product of two 16-bit values
+    is exact), ``y[t] = rn(p[t, 0] + p[t, 1] + ...)`` summed in fp32 from +0 in the order
+    ``j = 0 .. k-1``.  For ``k <= 2`` that equals
+    ``(d * routing_weights.to(d.dtype).unsqueeze(-1)).sum(dim=1)`` bit for bit: a sum of two fp32
+    terms is order-free.  For ``k > 2`` torch's reduction order is not promised, so the last bit
+    may differ from that expression.
+
+    The fused route is ONE launch (``nf4_gemm_bnb_moe_down``) plus at most casts of the ids and
+    the weights: ``d`` never leaves the launch's workspace, nothing synchronises with the host and
+    ``torch.cuda.graph`` captures the call.  fp32 weights and weights in the experts' dtype go to
+    the kernel as they are; any other dtype is cast to the experts' dtype first.  It is taken
+    exactly where ``nf4_moe_linear_bnb`` takes its fused route, when in addition the weights are
+    on the device with no gradient being recorded for them and
+    ``MOE_DOWN_ROUTED_MIN_P <= T*k <= MOE_DOWN_ROUTED_MAX_P``.  Everything else is the chain above
+    on tensors, which autograd follows to ``h`` and to ``routing_weights``; the GEMM's summation
+    order may differ between the routes, so the last bit of ``d`` may.
+    """
+    N = int(experts.out_features)
+    dtype = experts.dtype
+    dev = experts.weight.data.device
+    T, k, x_div, _ = _moe_args("nf4_moe_down_bnb", h, experts, expert_ids)
+    if tuple(routing_weights.shape) != (T, k) or not routing_weights.is_floating_point():
+        raise ValueError(f"nf4_moe_down_bnb: routing_weights must be a float [{T}, {k}] tensor, got "
+                         f"{routing_weights.dtype} {tuple(routing_weights.shape)}")
+    if routing_weights.device != dev:
+        raise RuntimeError(f"Expected all tensors to be on the same device, but found at least two devices, "
+                           f"{dev} and {routing_weights.device}!")
+    if out is not None and (tuple(out.shape) != (T, N) or out.dtype != dtype or out.device != dev
+                            or not out.is_contiguous()):
+        raise ValueError(f"nf4_moe_down_bnb: out must be a contiguous {dtype} [{T}, {N}] tensor on {dev}")
+    P = T * k
+    fused = (MOE_DOWN_ROUTED_MIN_P <= P <= MOE_DOWN_ROUTED_MAX_P and _moe_fusable(h, experts, P)
+             and not (torch.is_grad_enabled() and routing_weights.requires_grad))
+    if not fused:
+        if k == 0:
+            y = torch.zeros((T, N), dtype=dtype, device=dev)
+        else:
+            y = _moe_down_chain(nf4_moe_linear_bnb(h, experts, expert_ids), routing_weights)
+        if out is None:
+            return y
+        out.copy_(y)
+        return out
+    if out is None:
+        out = torch.empty((T, N), dtype=dtype, device=dev)
+    hc, ids = _moe_operands(h, expert_ids, dtype)
+    rw = routing_weights if routing_weights.dtype in (torch.float32, dtype) else routing_weights.to(dtype)
+    rw = rw.contiguous()
+    desc = _moe_desc(experts)
+    L = _lib.lib()
+    dp = ctypes.cast(ctypes.pointer(desc), ctypes.c_void_p)
+    with torch.cuda.device(dev):
+        ws_bytes = L.nf4_gemm_bnb_moe_down_workspace_bytes(P, dp, None)
+        ws = _moe_down_workspace(dev, ws_bytes)
+        rc = L.nf4_gemm_bnb_moe_down(hc.data_ptr(), ids.data_ptr(), P, x_div, k, rw.data_ptr(),
+                                     _lib.F32 if rw.dtype == torch.float32 else _dtype_code(dtype), dp, out.data_ptr(),
+                                     _dtype_code(dtype), ws.data_ptr(), ws_bytes, None,
+                                     torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "nf4 fused moe down gemm")
+    return out
+
+
 def nf4_moe_mlp_bnb(x: torch.Tensor, w1, w3, w2, expert_ids: torch.Tensor,
                     routing_weights: torch.Tensor) -> torch.Tensor:
     """A whole mixture-of-experts MLP block (Mixtral's) for ``Experts4bit`` stacks in bitsandbytes
     semantics: ``sum_j routing_weights[t, j] * w2_e(F.silu(w1_e(x[t])) * w3_e(x[t]))`` with
     ``e = expert_ids[t, j]``.  ``x`` is ``[T, H]``, ``expert_ids`` and ``routing_weights``
     ``[T, k]`` (the weights in any float dtype); returns ``[T, H]``.  It has no logic of its own:
-    ``nf4_moe_swiglu_bnb``, ``nf4_moe_linear_bnb`` and the weighted combine in torch, so it is
+    ``nf4_moe_swiglu_bnb``, then ``nf4_moe_down_bnb`` for ``k <= MOE_DOWN_MLP_MAX_K`` (bit for bit
+    the two lines below) or ``nf4_moe_linear_bnb`` and the weighted combine in torch, so it is
     capturable in a graph whenever its parts are, and autograd follows it to ``x``."""
     h = nf4_moe_swiglu_bnb(x, w1, w3, expert_ids)
+    if 1 <= expert_ids.shape[-1] <= MOE_DOWN_MLP_MAX_K and tuple(routing_weights.shape) == tuple(expert_ids.shape):
+        return nf4_moe_down_bnb(h, w2, expert_ids, routing_weights)
     d = nf4_moe_linear_bnb(h, w2, expert_ids)
     return (d * routing_weights.to(d.dtype).unsqueeze(-1)).sum(dim=1)

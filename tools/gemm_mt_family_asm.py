@@ -1,13 +1,13 @@
 """Device assembly and resource usage of the row-tiled GEMM family (nf4_gemm_mt.hip,
-nf4_gemm_mt_swiglu.hip, nf4_gemm_moe.hip, nf4_gemm_moe_swiglu.hip), and one tree's kernels against
-another's.
+nf4_gemm_mt_swiglu.hip, nf4_gemm_moe.hip, nf4_gemm_moe_swiglu.hip, nf4_gemm_moe_down.hip), and one
+tree's kernels against another's.
 
     python tools/gemm_mt_family_asm.py --out DIR [--csrc DIR] [--tables] [--against DIR]
 
 Compiles the family's sources of ``--csrc`` (default: this tree's; one that tree lacks is left out)
 to device assembly with the
 Makefile's flags (``--cuda-device-only -S -Rpass-analysis=kernel-resource-usage``, without
--Werror) into ``--out``.  ``--tables`` rewrites profiles/gemm_{mt,mt_swiglu,moe,moe_swiglu}/resource_usage.txt
+-Werror) into ``--out``.  ``--tables`` rewrites profiles/gemm_{mt,mt_swiglu,moe,moe_swiglu,moe_down}/resource_usage.txt
 from the compiler's remarks.  ``--against DIR`` (an ``--out`` of another tree, e.g. the parent
 commit's sources) compares kernel by kernel: the instruction streams after dropping comments and
 directives and renumbering labels, and where they differ scratch, spills, waves per SIMD,
@@ -42,7 +42,8 @@ FLAGS = makefile_flags()
 FAMILY = {"nf4_gemm_mt": ("gemm_mt", "nf4_gemm_mt_kernel", 1104),
           "nf4_gemm_mt_swiglu": ("gemm_mt_swiglu", "nf4_gemm_mt_swiglu_kernel", 2128),
           "nf4_gemm_moe": ("gemm_moe", "nf4_gemm_moe_kernel", 2128),
-          "nf4_gemm_moe_swiglu": ("gemm_moe_swiglu", "nf4_gemm_moe_swiglu_kernel", 3152)}
+          "nf4_gemm_moe_swiglu": ("gemm_moe_swiglu", "nf4_gemm_moe_swiglu_kernel", 3152),
+          "nf4_gemm_moe_down": ("gemm_moe_down", "nf4_gemm_moe_kernel", 2128)}
 FIELDS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch",
           "Occupancy [waves/SIMD]": "waves", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill",
           "LDS Size [bytes/block]": "static_lds"}
@@ -97,7 +98,7 @@ def params(name):
 def write_table(out, src):
     prof, kernel, tables = FAMILY[src]
     ks = kernels(out, src)
-    rows = [f"{kernel}<DT, MT, SM, WV>: hipcc {' '.join(f for f in FLAGS if f not in ('-fPIC', '-Wall', '-S', '--cuda-device-only'))}",
+    rows = [f"{kernel}<DT, MT, SM, WV{', true' if src == 'nf4_gemm_moe_down' else ''}>: hipcc {' '.join(f for f in FLAGS if f not in ('-fPIC', '-Wall', '-S', '--cuda-device-only'))}",
             f"(LDS is dynamic: two x buffers of 16 MT rows x 256 bytes + {tables} bytes behind them; static LDS 0."
             "  Columns: the compiler's remarks; SGPRs = TotalSGPRs; spills: SGPR + VGPR; LDS bytes: computed as the"
             " plan header does, not measured)", "",
@@ -112,7 +113,9 @@ def write_table(out, src):
                 rows.append(f"{'bf16' if dt else 'f16':<5}{mt:>10} {'nested' if sm == 1 else 'single':<7}{wv:>6}"
                             f"{k['vgprs']:>7}{k['agprs']:>7}{k['sgprs']:>7}{k['scratch']:>9}{k['sgpr_spill'] + k['vgpr_spill']:>8}"
                             f"{k['waves']:>12}{2 * 16 * mt * 256 + tables:>11}{sum(i.startswith('v_mfma') for i in k['insts']):>8}")
-    with open(os.path.join(REPO, "profiles", prof, "resource_usage.txt"), "w") as f:
+    # (profiles/gemm_moe_down/resource_usage.txt is the expert GEMM's own kernels against the parent's)
+    table = "resource_usage_down.txt" if src == "nf4_gemm_moe_down" else "resource_usage.txt"
+    with open(os.path.join(REPO, "profiles", prof, table), "w") as f:
         f.write("\n".join(rows) + "\n")
 
 
@@ -122,10 +125,11 @@ def compare(out, base):
         if not os.path.exists(os.path.join(base, src + ".s")):
             print(f"{src}: not in the other tree")
             continue
-        new, old = kernels(out, src), kernels(base, src)
+        # by template parameters: a parameter added behind them changes the mangled names
+        new, old = ({params(n): k for n, k in kernels(d, src).items()} for d in (out, base))
         assert sorted(new) == sorted(old) and len(new) == 32, (src, len(new), len(old))
         same = 0
-        for name in sorted(new, key=params):
+        for name in sorted(new):
             n, o = new[name], old[name]
             if n["insts"] == o["insts"]:
                 same += 1
@@ -133,7 +137,7 @@ def compare(out, base):
             mf = [sum(i.startswith("v_mfma") for i in k["insts"]) for k in (n, o)]
             keep = all(n[f] == o[f] for f in ("scratch", "sgpr_spill", "vgpr_spill", "waves", "agprs", "static_lds")) and mf[0] == mf[1]
             bad += not keep
-            print(f"{src} DT,MT,SM,WV={params(name)}: streams differ ({len(o['insts'])} -> {len(n['insts'])} instructions); "
+            print(f"{src} DT,MT,SM,WV={name}: streams differ ({len(o['insts'])} -> {len(n['insts'])} instructions); "
                   f"VGPRs {o['vgprs']} -> {n['vgprs']}, SGPRs {o['sgprs']} -> {n['sgprs']}, AGPRs {o['agprs']} -> {n['agprs']}, "
                   f"scratch {o['scratch']} -> {n['scratch']}, spills {o['sgpr_spill'] + o['vgpr_spill']} -> "
                   f"{n['sgpr_spill'] + n['vgpr_spill']}, waves/SIMD {o['waves']} -> {n['waves']}, v_mfma {mf[1]} -> {mf[0]}"
