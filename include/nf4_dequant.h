@@ -655,6 +655,50 @@ int nf4_gemm_bnb_moe_down(const void* x, const void* expert_ids, int64_t P, int3
                           int32_t out_dtype, void* workspace, size_t workspace_bytes,
                           const nf4_gemm_cfg* cfg, void* hip_stream);
 
+/* The low-rank adapter tail of a Linear4bit (LoRA), one launch for up to NF4DQ_LORA_GROUP_MAX
+ * adapters that share the activations x [M][K]:  y_i = base_i + scale_i * B_i (A_i x).
+ * `mats` points at `count` nf4_lora_mat descriptors ON THE HOST (read during the call only).
+ * With rn = round-to-nearest-even to `dtype` (fp16 / bf16: x, A [r][K], B [N][r], base [M][N] and
+ * y [M][N] all have it, dense and row-major), per adapter
+ *   t[m][j] = rn(sum_k x[m][k] * A[j][k])          fp32 accumulation
+ *   u[m][n] = rn(sum_j t[m][j] * B[n][j])          fp32 accumulation
+ *   v[m][n] = rn(float(u[m][n]) * scale)           one fp32 product, rounded once more
+ *   y[m][n] = rn(float(base[m][n]) + float(v[m][n]))     base NULL: y = v
+ * -- the rounding chain of `result + lora_B(lora_A(x)) * scaling` on 16-bit tensors.  The order of
+ * the two sums is the kernel's: a function of (M, K, the r and N of the group, tile_n, waves)
+ * alone -- no float atomics, the same bits on every call.  base == y (in place) is the normal use:
+ * every output element is read and written once, by one lane.  Two adapters of one call must not
+ * share output elements.
+ * Domain: 1 <= M <= NF4DQ_LORA_MAX_M, K % 32 == 0, N % 16 == 0, r % 8 == 0 and
+ * 8 <= r <= NF4DQ_LORA_MAX_R, 1 <= count <= NF4DQ_LORA_GROUP_MAX, every pointer 16-byte aligned.
+ * Codes: a null x / mats / A / B / y, a dtype that is not fp16 or bf16, a count or an r outside
+ * its limits, an invalid cfg: NF4DQ_ERR_ARG.  M, K, N or r % 8 outside the domain, a misaligned
+ * pointer: NF4DQ_ERR_SHAPE.  K or N above 2^22: NF4DQ_ERR_TOO_LARGE.  Checked in that order.
+ * cfg NULL = the library's choice for (M, K, the group's N and r, CU count); a nf4_lora_cfg names
+ * tile_n in {16, 32, 64, 128, 256} and waves in {1, 2, 4} and never falls back.
+ * The grid is (adapter, tile of tile_n columns); every workgroup forms its adapter's whole t in
+ * LDS (K split over its waves, partials summed in wave order), then each wave takes 16-column
+ * strips of the tile.  No workspace, no host read of device memory, no workgroup waits for
+ * another.  Asynchronous on `hip_stream`; one launch; allocates nothing; capturable in a graph. */
+#define NF4DQ_LORA_MAX_M 128
+#define NF4DQ_LORA_MAX_R 128
+#define NF4DQ_LORA_GROUP_MAX 8 /* = NF4DQ_GEMM_GROUP_MAX */
+typedef struct {
+    const void* A;    /* [r][K] */
+    const void* B;    /* [N][r] */
+    const void* base; /* [M][N], or NULL; may be y */
+    void* y;          /* [M][N] */
+    int64_t N;
+    int32_t r;
+    float scale;
+} nf4_lora_mat;
+typedef struct {
+    int32_t tile_n; /* columns per workgroup */
+    int32_t waves;  /* waves per workgroup */
+} nf4_lora_cfg;
+int nf4_lora_add(const void* x, int64_t M, int64_t K, const void* mats, int32_t count, int32_t dtype,
+                 const void* cfg, void* hip_stream);
+
 /* The split-K hand-off never hangs: a reducer that has polled a partner slice's
  * entries 2^16 times without seeing them gives up, reads them as NaN and sets a
  * sticky error word in the workspace header.  This call waits for `hip_stream`,

@@ -117,6 +117,26 @@ class MoeExperts(ctypes.Structure):
                 ("blocksize", ctypes.c_int32), ("blocksize2", ctypes.c_int32)]
 
 
+LORA_MAX_M = 128     # NF4DQ_LORA_MAX_M: rows of one nf4_lora_add launch
+LORA_MAX_R = 128     # NF4DQ_LORA_MAX_R: the largest adapter rank
+LORA_GROUP_MAX = 8   # NF4DQ_LORA_GROUP_MAX: adapters of one nf4_lora_add launch
+LORA_TILES = (16, 32, 64, 128, 256)  # nf4_lora_cfg.tile_n
+LORA_WAVES = (1, 2, 4)               # nf4_lora_cfg.waves
+
+
+class LoraMat(ctypes.Structure):
+    """nf4_lora_mat (include/nf4_dequant.h): one adapter of nf4_lora_add."""
+
+    _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("base", ctypes.c_void_p), ("y", ctypes.c_void_p),
+                ("N", ctypes.c_int64), ("r", ctypes.c_int32), ("scale", ctypes.c_float)]
+
+
+class LoraCfg(ctypes.Structure):
+    """nf4_lora_cfg (include/nf4_dequant.h)."""
+
+    _fields_ = [("tile_n", ctypes.c_int32), ("waves", ctypes.c_int32)]
+
+
 class GemmCfg(ctypes.Structure):
     """nf4_gemm_cfg (include/nf4_dequant.h)."""
 
@@ -187,6 +207,8 @@ SIGNATURES = {
     "nf4_gemm_bnb_moe_down_workspace_bytes": (ctypes.c_size_t, [_I64, _P, ctypes.POINTER(GemmCfg)]),
     "nf4_gemm_bnb_moe_down": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _I32, _P, _P, _I32, _P, ctypes.c_size_t,
                                              ctypes.POINTER(GemmCfg), _P]),
+    # `mats`: const void* in the header, pointing at LoraMat[count]; `cfg`: NULL or one LoraCfg
+    "nf4_lora_add": (ctypes.c_int, [_P, _I64, _I64, _P, _I32, _I32, _P, _P]),
     "nf4_gemm_check_workspace": (ctypes.c_int, [_P, ctypes.c_size_t, _P]),
     "nf4_strerror": (ctypes.c_char_p, [ctypes.c_int]),
     "nf4_version": (ctypes.c_char_p, []),

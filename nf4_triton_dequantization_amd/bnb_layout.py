@@ -244,6 +244,51 @@ class Linear4bit(nn.Module):
         return nf4_linear_bnb(x, self, self.bias)
 
 
+class LoraLinear4bit(nn.Module):
+    """A ``Linear4bit`` with a low-rank (LoRA) adapter, the inference form of PEFT's wrapper:
+    ``base_layer(x) + lora_B(lora_A(x)) * scaling``.  There is NO dropout (PEFT's ``lora_dropout``
+    is the identity at inference) and one adapter.
+
+    ``base_layer`` is the wrapped ``Linear4bit``; ``lora_A`` (``[r, in_features]``) and ``lora_B``
+    (``[out_features, r]``) are bias-free ``nn.Linear``, so the parameter names ``lora_A.weight``
+    and ``lora_B.weight`` are PEFT's and an adapter state dict loads once its prefix (and the
+    adapter name) is stripped; ``scaling`` is a float (``lora_alpha / r``).  ``forward`` is
+    ``kernel.nf4_linear_lora_bnb``: one fused launch for the whole tail where that is routed, the
+    composite -- which autograd follows to ``lora_A`` and ``lora_B`` -- everywhere else.
+    """
+
+    def __init__(self, base_layer: Linear4bit, lora_A: nn.Linear, lora_B: nn.Linear, scaling: float):
+        super().__init__()
+        self.base_layer = base_layer
+        self.lora_A = lora_A
+        self.lora_B = lora_B
+        self.scaling = float(scaling)
+        self.in_features, self.out_features = base_layer.in_features, base_layer.out_features
+        self.r = int(lora_A.out_features)
+
+    @classmethod
+    def from_linear4bit(cls, base: Linear4bit, r: int, lora_alpha: float, dtype=None):
+        """A fresh adapter of rank ``r`` on ``base`` with PEFT's initialisation: kaiming-uniform
+        ``lora_A`` (``a = sqrt(5)``), zero ``lora_B`` -- so the module starts as ``base`` exactly
+        -- and ``scaling = lora_alpha / r``.  ``dtype`` defaults to ``quant_state.dtype`` (the
+        fused route needs the two equal); the adapter lives on the weight's device."""
+        if r < 1:
+            raise ValueError("LoraLinear4bit.from_linear4bit: r must be positive")
+        dev = base.weight.data.device
+        dtype = dtype if dtype is not None else base.weight.quant_state.dtype
+        lora_A = nn.Linear(base.in_features, r, bias=False, device=dev, dtype=dtype)
+        lora_B = nn.Linear(r, base.out_features, bias=False, device=dev, dtype=dtype)
+        nn.init.kaiming_uniform_(lora_A.weight, a=math.sqrt(5))
+        nn.init.zeros_(lora_B.weight)
+        return cls(base, lora_A, lora_B, lora_alpha / r)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        from .kernel import nf4_linear_lora_bnb
+
+        return nf4_linear_lora_bnb(x, self.base_layer, self.lora_A.weight, self.lora_B.weight, self.scaling,
+                                   self.base_layer.bias)
+
+
 class Embedding4bit(nn.Module):
     """``bitsandbytes.nn.Embedding4bit`` / ``EmbeddingNF4`` stand-in: a token embedding whose
     ``[num_embeddings, embedding_dim]`` table is NF4 storage (a ``Params4bit``).

@@ -1383,3 +1383,126 @@ def nf4_moe_mlp_bnb(x: torch.Tensor, w1, w3, w2, expert_ids: torch.Tensor,
         return nf4_moe_down_bnb(h, w2, expert_ids, routing_weights)
     d = nf4_moe_linear_bnb(h, w2, expert_ids)
     return (d * routing_weights.to(d.dtype).unsqueeze(-1)).sum(dim=1)
+
+
+# Rows at which nf4_linear_lora_bnb and nf4_linear_lora_bnb_grouped take the fused adapter launch
+# (nf4_lora_add).  Set from tools/bench_lora.py's measurement and from nothing else: a row count is
+# routed only where, at every shape and rank measured, the slower of the launch's two runs beats
+# the faster of the composite's two runs by more than the spread of a route's rounds
+# (profiles/lora/, README, DESIGN section 4b "The adapter tail").  Measured at 4096^2, 1024x4096,
+# 14336x4096 and 4096x14336 with r = 16 and 64: the launch wins 3 of 8 tail cells at one row,
+# 3 of 8 at 8, 0 of 8 at 32 and none at 64 or 128 (it wins at r = 16 with K = 4096 and loses at r = 64
+# and at K = 14336), so no row count meets the rule: an empty range (MIN above MAX), the launch is
+# reached through the C entry alone and both functions take the composite at every row count.
+LORA_ROUTED_MIN_M = 1
+LORA_ROUTED_MAX_M = 0
+
+
+def _lora_composite(y: torch.Tensor, x: torch.Tensor, A: torch.Tensor, B: torch.Tensor, scaling: float) -> torch.Tensor:
+    """The definition of the adapter tail (PEFT's expression): what autograd follows."""
+    t = torch.nn.functional.linear(x.to(A.dtype), A)
+    u = torch.nn.functional.linear(t, B)
+    return y + (u * scaling).to(y.dtype)
+
+
+def _lora_fusable(x: torch.Tensor, module, A: torch.Tensor, B: torch.Tensor, M: int) -> bool:
+    """nf4_linear_lora_bnb's fused-path rules (its docstring) for one adapter."""
+    dtype = module.weight.quant_state.dtype
+    dev = module.weight.data.device
+    N, K = int(module.out_features), int(module.in_features)
+    if not (dev.type == "cuda" and x.device == dev and A.device == dev and B.device == dev
+            and dtype in (torch.float16, torch.bfloat16) and A.dtype == dtype and B.dtype == dtype
+            and max(1, LORA_ROUTED_MIN_M) <= M <= min(LORA_ROUTED_MAX_M, _lib.LORA_MAX_M)
+            and A.dim() == 2 and B.dim() == 2):
+        return False
+    r = int(A.shape[0])
+    return (tuple(A.shape) == (r, K) and tuple(B.shape) == (N, r) and r % 8 == 0 and 8 <= r <= _lib.LORA_MAX_R
+            and K % 32 == 0 and K >= 32 and N % 16 == 0 and N >= 16
+            and A.is_contiguous() and B.is_contiguous() and A.data_ptr() % 16 == 0 and B.data_ptr() % 16 == 0
+            and not (torch.is_grad_enabled() and (x.requires_grad or A.requires_grad or B.requires_grad)))
+
+
+def _lora_add(x: torch.Tensor, M: int, K: int, dtype: torch.dtype, items) -> None:
+    """ONE nf4_lora_add launch: ``items`` is [(y [.., N] contiguous, updated in place, A, B, scaling)]."""
+    dev = x.device
+    xc = x.reshape(M, K)
+    if xc.dtype != dtype:
+        xc = xc.to(dtype)
+    xc = xc.contiguous()
+    if xc.data_ptr() % 16:
+        xc = xc.clone()  # a view at an odd offset: the entry loads 16 bytes at a time
+    mats = (_lib.LoraMat * len(items))()
+    for i, (y, A, B, scaling) in enumerate(items):
+        mats[i] = _lib.LoraMat(A.data_ptr(), B.data_ptr(), y.data_ptr(), y.data_ptr(), int(B.shape[0]),
+                               int(A.shape[0]), float(scaling))
+    with torch.cuda.device(dev):
+        rc = _lib.lib().nf4_lora_add(xc.data_ptr(), M, K, ctypes.cast(mats, ctypes.c_void_p), len(items),
+                                     _dtype_code(dtype), None, torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "nf4 fused lora add")
+
+
+def _lora_base_in_place(y: torch.Tensor, dtype: torch.dtype) -> bool:
+    return y.dtype == dtype and y.is_contiguous() and y.data_ptr() % 16 == 0 and not y.requires_grad
+
+
+def nf4_linear_lora_bnb(x: torch.Tensor, module, lora_A: torch.Tensor, lora_B: torch.Tensor, scaling: float,
+                        bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``W x + b + scaling * B (A x)``: a ``Linear4bit`` in bitsandbytes semantics with a low-rank
+    (LoRA) adapter, ``lora_A`` ``[r, K]`` and ``lora_B`` ``[N, r]`` (PEFT's ``lora_A.weight`` and
+    ``lora_B.weight``).  Its definition, which is also its fallback, is PEFT's expression::
+
+        y = nf4_linear_bnb(x, module, bias)
+        t = F.linear(x.to(A.dtype), A)
+        u = F.linear(t, B)
+        y + (u * scaling).to(y.dtype)
+
+    The fused route runs the base through ``nf4_linear_bnb`` and the whole tail as ONE launch
+    (``nf4_lora_add``) that updates the base's result in place, with the rounding chain of the
+    expression on 16-bit tensors (``t``, ``u``, the scaled ``u`` and the sum each rounded once);
+    nothing synchronises with the host and ``torch.cuda.graph`` captures the call.  It is taken
+    when the tensors are on the GPU, the adapter's dtype equals ``quant_state.dtype`` and is fp16
+    or bf16, ``K % 32 == 0``, ``N % 16 == 0``, ``r % 8 == 0`` with ``8 <= r <= 128``, the adapter
+    is contiguous and 16-byte aligned, ``LORA_ROUTED_MIN_M <= M <= LORA_ROUTED_MAX_M`` rows and no
+    gradient is being recorded for ``x``, ``lora_A`` or ``lora_B``.  Everything else -- fp32
+    adapters (PEFT's default unless cast), training, CPU tensors, other ranks and row counts --
+    takes the composite, which autograd follows.  The summation order of the two products may
+    differ between the routes, so the last bits may.
+    """
+    y = nf4_linear_bnb(x, module, bias)
+    K = int(module.in_features)
+    M = x.numel() // K if K else 0
+    dtype = module.weight.quant_state.dtype
+    if not (_lora_fusable(x, module, lora_A, lora_B, M) and _lora_base_in_place(y, dtype)):
+        return _lora_composite(y, x, lora_A, lora_B, scaling)
+    _lora_add(x, M, K, dtype, [(y, lora_A, lora_B, scaling)])
+    return y
+
+
+def nf4_linear_lora_bnb_grouped(x: torch.Tensor, modules: Sequence, adapters: Sequence,
+                                biases: Optional[Sequence] = None) -> List[torch.Tensor]:
+    """``nf4_linear_lora_bnb`` for ``Linear4bit`` weights that share the input x (q/k/v, gate/up):
+    ``adapters[i]`` is ``(lora_A, lora_B, scaling)`` or ``None`` for a module without one.  The
+    base goes through ``nf4_linear_bnb_grouped``; ALL adapters that meet ``nf4_linear_lora_bnb``'s
+    fused-path rules go in ONE ``nf4_lora_add`` launch when there are at most ``LORA_GROUP_MAX``
+    of them (each updates its module's result in place), every other adapter takes the composite.
+    """
+    modules = list(modules)
+    adapters = list(adapters)
+    if len(adapters) != len(modules):
+        raise ValueError("nf4_linear_lora_bnb_grouped: one adapter (or None) per module")
+    ys = nf4_linear_bnb_grouped(x, modules, biases)
+    if not modules:
+        return ys
+    K = int(modules[0].in_features)
+    M = x.numel() // K if K and x.shape[-1] == K else 0
+    dtype = modules[0].weight.quant_state.dtype
+    fused = [ad is not None and int(mod.in_features) == K and mod.weight.quant_state.dtype == dtype
+             and _lora_fusable(x, mod, ad[0], ad[1], M) and _lora_base_in_place(y, dtype)
+             for mod, ad, y in zip(modules, adapters, ys)]
+    if not 1 <= sum(fused) <= _lib.LORA_GROUP_MAX:
+        fused = [False] * len(modules)
+    items = [(y, ad[0], ad[1], ad[2]) for y, ad, f in zip(ys, adapters, fused) if f]
+    if items:
+        _lora_add(x, M, K, dtype, items)
+    return [y if f or ad is None else _lora_composite(y, x, ad[0], ad[1], ad[2])
+            for y, ad, f in zip(ys, adapters, fused)]
