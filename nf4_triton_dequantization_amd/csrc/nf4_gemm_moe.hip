@@ -10,31 +10,7 @@ template <int SM>
 int launch_moe(const nf4gemm::MoeCall& a, const nf4_gemm_cfg& cfg, hipStream_t st) {
     const nf4_moe_experts& e = *a.ex;
     const MoePlan p = moe_plan(cfg, a.P, e.experts, e.N, e.K);
-    MoeArgs A{};
-    A.packed = e.packed;
-    A.a1 = e.absmax_q;
-    A.a2 = e.absmax2;
-    A.code2 = e.code2;
-    A.offset = e.offset;
-    A.ids = reinterpret_cast<const int32_t*>(a.ids);
-    A.x = a.x;
-    A.y = a.y;
-    A.counters = mt_counters(a.workspace);
-    A.slab = mt_slab(a.workspace, cfg);
-    A.packed_stride = e.packed_stride;
-    A.nb_stride = e.nb_stride;
-    A.n2_stride = e.n2_stride;
-    A.code2_stride = e.code2_stride;
-    A.P = (uint32_t)a.P;
-    A.E = (uint32_t)e.experts;
-    A.N = (uint32_t)e.N;
-    A.K = (uint32_t)e.K;
-    A.x_div = (uint32_t)a.x_div;
-    A.tiles = p.tiles;
-    A.ksplit = (uint32_t)cfg.ksplit;
-    A.cps = p.cps;
-    A.chunks = p.chunks;
-    A.sh2 = mt_log2_blocksize2(e.single, e.blocksize2);
+    const MoeArgsT<1> A = moe_fill<1>(a, a.y, p, cfg);
     int rc = NF4DQ_ERR_ARG;
     pick<NF4DQ_BF16, NF4DQ_F16>(a.dtype, [&](auto DT) {
         pick<2, 4, 6, 8>((int)p.row_tiles, [&](auto MT) {

@@ -1,10 +1,14 @@
-// nf4_gemm_moe_dev.h -- the device code of the fused NF4 expert GEMM of a mixture-of-experts
-// block in bitsandbytes semantics, once: nf4_gemm_moe.hip (nf4_gemm_bnb_moe: the products of the
-// (token, choice) pairs) and nf4_gemm_moe_down.hip (nf4_gemm_bnb_moe_down: the same products,
-// combined per token with the routing weights inside the launch) launch this one kernel template
-// with the compile-time flag DOWN false and true.  With DOWN false every DOWN branch is discarded
-// and the 32 instantiations have the instruction streams nf4_gemm_moe.hip's own kernel had
-// (profiles/gemm_moe_down/resource_usage.txt).
+// nf4_gemm_moe_dev.h -- the device code of the fused NF4 expert kernels of a mixture-of-experts
+// block in bitsandbytes semantics, once.  Three launchers instantiate this one kernel template:
+//  * nf4_gemm_moe.hip (nf4_gemm_bnb_moe: the products of the (token, choice) pairs): DOWN false,
+//    W = 1;
+//  * nf4_gemm_moe_down.hip (nf4_gemm_bnb_moe_down: the same products, combined per token with the
+//    routing weights inside the launch): DOWN true, W = 1;
+//  * nf4_gemm_moe_swiglu.hip (nf4_gemm_bnb_moe_swiglu: h = silu(g) * u over a gate and an up stack):
+//    DOWN false, W = 2.
+// DOWN and W are compile-time: every branch of the other instantiations is discarded.  What the
+// merge of the three kernels into this template moved in the generated code, and what it cost, is
+// in profiles/gemm_moe_family/README.md.
 //
 // y[p][N] = x[p / x_div][K] . W_e[N][K]^T with e = expert_ids[p] read ON THE DEVICE and W_e the
 // 16-bit weights nf4_dequant_bnb writes for expert e, bit for bit.  One launch covers every
@@ -35,6 +39,21 @@
 // Split-K: the row-tiled kernel's hand-off with the slab indexed by pair and one ticket per
 // (expert, column tile).  Nobody waits for anybody: there is no poll.
 //
+// W: what a wave's two strips are (MtStrips<W>) and what becomes of their sums.  All of the above
+// holds for both.
+//  * W = 1: two 16-column strips of ONE stack, 32 WV columns of y a workgroup, MtSumOut, one fp32
+//    plane per slice;
+//  * W = 2: h[p][I] = silu(g) * u with g = x[p / x_div] . Wg_e^T and u = x[p / x_div] . Wu_e^T.
+//    Strip 0 is rows col .. col + 15 of the expert's gate weight and strip 1 the same rows of its
+//    up weight, each from its own stack: base pointers (base + e * stride), statistics,
+//    blocksize2, offset (offset[e]) and code2 table (two tables in LDS, c2tab + 256 wt, each from
+//    code2 + e * code2_stride of its own stack).  A workgroup owns 16 WV columns of h;
+//    acc[mt][0][i] and acc[mt][1][i] are g and u of ONE element of h in one lane.  g and u are
+//    what W = 1 stores for the gate and the up stack (exact 16-bit weights, fp32 MFMA sums, one
+//    RNE), the chain SgOut's (swiglu16 of nf4_gemm_mt_dev.h); a slice stores two planes,
+//    [ksplit][2][P][I], and the slice that draws the last ticket sums each in slice order over the
+//    expert's listed rows and applies the chain.
+//
 // DOWN: out[t][N] = rn(sum_j rn(y[t k + j] * rn(rw[t k + j]))) with y[p] the 16-bit row above.
 //  * A.y is a 16-bit scratch [P][N] in the workspace: the workgroup (one K slice) or the
 //    slice-order reducer (several) stores the expert's finished rows there through the paths
@@ -55,22 +74,59 @@
 
 namespace {
 
-struct MoeArgs {
-    const uint8_t* packed;  // [E] x [N][K/2], packed_stride bytes apart
-    const uint8_t* a1;      // nested: absmax bytes [N K / 64] per expert, nb_stride apart
-    const float* a2;        // nested: absmax2; single: the fp32 absmax; n2_stride floats apart
-    const float* code2;     // nested: [256], code2_stride floats apart (0: shared)
-    const float* offset;    // nested: [E] or null (= 0)
-    const int32_t* ids;     // [P]
-    const void* x;          // [ceil(P / x_div)][K]
-    void* y;                // [P][N]
-    float* slab;            // [ksplit][P][N] (ksplit > 1)
-    uint32_t* counters;     // one ticket per (expert, column tile)
-    int64_t packed_stride, nb_stride, n2_stride, code2_stride;
+// A launch over W stacks of experts (1: one weight; 2: gate, up).  Per-stack fields are arrays of W.
+template <int W>
+struct MoeArgsT {
+    const uint8_t* packed[W];  // [E] x [N][K/2], packed_stride bytes apart
+    const uint8_t* a1[W];      // nested: absmax bytes [N K / 64] per expert, nb_stride apart
+    const float* a2[W];        // nested: absmax2; single: the fp32 absmax; n2_stride floats apart
+    const float* code2[W];     // nested: [256], code2_stride floats apart (0: shared)
+    const float* offset[W];    // nested: [E] or null (= 0)
+    const int32_t* ids;        // [P]
+    const void* x;             // [ceil(P / x_div)][K]
+    void* y;                   // [P][N]
+    float* slab;               // [ksplit][W][P][N] (ksplit > 1)
+    uint32_t* counters;        // one ticket per (expert, column tile)
+    int64_t packed_stride[W], nb_stride[W], n2_stride[W], code2_stride[W];
     uint32_t P, E, N, K, x_div;
     uint32_t tiles, ksplit, cps, chunks;  // column tiles, K slices, chunks per slice, K / 128
-    uint32_t sh2;           // log2(blocksize2)
+    uint32_t sh2[W];           // log2(blocksize2)
 };
+
+// The fill every launcher shares: the stacks, the call (Call: MoeCall or MsgCall) and the plan.
+// y: where the kernel stores its rows (the caller's output, or DOWN's scratch).
+template <int W, class Call>
+inline MoeArgsT<W> moe_fill(const Call& a, void* y, const nf4gemm::MoePlan& p, const nf4_gemm_cfg& cfg) {
+    MoeArgsT<W> A{};
+    for (int i = 0; i < W; ++i) {
+        const nf4_moe_experts& e = a.ex[i];
+        A.packed[i] = e.packed;
+        A.a1[i] = e.absmax_q;
+        A.a2[i] = e.absmax2;
+        A.code2[i] = e.code2;
+        A.offset[i] = e.offset;
+        A.packed_stride[i] = e.packed_stride;
+        A.nb_stride[i] = e.nb_stride;
+        A.n2_stride[i] = e.n2_stride;
+        A.code2_stride[i] = e.code2_stride;
+        A.sh2[i] = mt_log2_blocksize2(e.single, e.blocksize2);
+    }
+    A.ids = reinterpret_cast<const int32_t*>(a.ids);
+    A.x = a.x;
+    A.y = y;
+    A.counters = mt_counters(a.workspace);
+    A.slab = mt_slab(a.workspace, cfg);
+    A.P = (uint32_t)a.P;
+    A.E = (uint32_t)a.ex[0].experts;
+    A.N = (uint32_t)a.ex[0].N;
+    A.K = (uint32_t)a.ex[0].K;
+    A.x_div = (uint32_t)a.x_div;
+    A.tiles = p.tiles;
+    A.ksplit = (uint32_t)cfg.ksplit;
+    A.cps = p.cps;
+    A.chunks = p.chunks;
+    return A;
+}
 
 // A 16-bit value of the output dtype, widened to fp32 (exact).
 template <int DT>
@@ -121,30 +177,38 @@ __device__ inline void moe_combine(const MoeCombine& C, uint32_t col0) {
 
 // A launch's arguments: the expert GEMM's, and with DOWN the combine's behind them.
 struct MoeDownArgs {
-    MoeArgs g;
+    MoeArgsT<1> g;
     MoeCombine c;
 };
-template <bool DOWN>
-using MoeKernArgs = std::conditional_t<DOWN, MoeDownArgs, MoeArgs>;
-__device__ __forceinline__ const MoeArgs& moe_gemm_args(const MoeArgs& a) { return a; }
-__device__ __forceinline__ const MoeArgs& moe_gemm_args(const MoeDownArgs& a) { return a.g; }
+template <bool DOWN, int W>
+using MoeKernArgs = std::conditional_t<DOWN, MoeDownArgs, MoeArgsT<W>>;
+template <int W>
+__device__ __forceinline__ const MoeArgsT<W>& moe_gemm_args(const MoeArgsT<W>& a) { return a; }
+__device__ __forceinline__ const MoeArgsT<1>& moe_gemm_args(const MoeDownArgs& a) { return a.g; }
 
 // (the second launch bound, waves per SIMD: with two row tiles the kernel needs no more than 256
 // registers, so a CU holds two workgroups of 4 waves -- what the plan's K-slice rule counts on,
 // moe_resident(); more than two would spill)
-// (one kernel template, not a shared body behind two kernels: inlined from a function of its own
-// the expert GEMM did not keep its registers and spills)
-template <int DT, int MT, int SM, int WV, bool DOWN = false>
-__global__ __launch_bounds__(64 * WV, MT <= 2 ? 2 : 1) void nf4_gemm_moe_kernel(const MoeKernArgs<DOWN> KA) {
-    const MoeArgs& A = moe_gemm_args(KA);
+// (one kernel template, not a shared body behind several kernels: inlined from a function of its
+// own the expert GEMM did not keep its registers and spills.  Where W = 1 and W = 2 place a
+// statement differently -- the offset loads, the row and block index in wload, the slab address --
+// each has the order of the kernel it was merged from: with one order for both, the other's
+// instruction streams move and the 128-pair SwiGLU launch measured up to 1 % slower,
+// profiles/gemm_moe_family/README.md)
+template <int DT, int MT, int SM, int WV, bool DOWN = false, int W = 1>
+__global__ __launch_bounds__(64 * WV, MT <= 2 ? 2 : 1) void nf4_gemm_moe_kernel(const MoeKernArgs<DOWN, W> KA) {
+    static_assert(!DOWN || W == 1, "the routed sum is behind one stack's products");
+    using Strips = MtStrips<W>;
+    using Out = std::conditional_t<W == 2, SgOut<DT>, MtSumOut<DT>>;
+    const MoeArgsT<W>& A = moe_gemm_args(KA);
     constexpr uint32_t T = 64u * WV;
     constexpr uint32_t kBuf = 16u * MT * kMtRowBytes;
     constexpr int NP = 16 * MT * 16 / (int)T;  // 16-byte pieces of a stage per thread
-    constexpr uint32_t COLS = 32u * WV;
+    constexpr uint32_t COLS = Strips::kWaveCols * WV;
     static_assert(16 * MT * 16 % T == 0, "a stage divides over the threads");
-    extern __shared__ __attribute__((aligned(16))) char smem[];  // [x buffer 0][x buffer 1][code2][codes][flag][x rows][y rows]
+    extern __shared__ __attribute__((aligned(16))) char smem[];  // [x buffer 0][x buffer 1][code2 x W][codes][flag][x rows][y rows]
     float* c2tab = reinterpret_cast<float*>(smem + 2u * kBuf);
-    float* lut = c2tab + 256;
+    float* lut = c2tab + 256 * W;
     uint32_t* flag = reinterpret_cast<uint32_t*>(lut + 16);
     uint32_t* srow = flag + 4;                       // staged row -> row of x
     uint32_t* prow = srow + NF4DQ_MOE_MAX_PAIRS;     // staged row -> pair (row of y)
@@ -198,20 +262,26 @@ __global__ __launch_bounds__(64 * WV, MT <= 2 ? 2 : 1) void nf4_gemm_moe_kernel(
     }
     const uint32_t my_tiles = (cnt + 15u) >> 4;  // row tiles this expert fills
 
-    const uint32_t col0 = tile * COLS + wave * 32u;
+    const uint32_t col0 = tile * COLS + wave * Strips::kWaveCols;
     const uint32_t c_begin = ks * A.cps < A.chunks ? ks * A.cps : A.chunks;
     const uint32_t c_end = c_begin + A.cps < A.chunks ? c_begin + A.cps : A.chunks;
     const uint32_t bpr = A.K >> 6, kb = A.K >> 1;
-    const uint8_t* packed = A.packed + (int64_t)ex * A.packed_stride;
-    const uint8_t* a1 = SM == kScaleBnb ? A.a1 + (int64_t)ex * A.nb_stride : nullptr;
-    const float* a2 = A.a2 + (int64_t)ex * A.n2_stride;
-
-    if constexpr (SM == kScaleBnb) {
-        const float* code2 = A.code2 + (int64_t)ex * A.code2_stride;
-        for (uint32_t i = tid; i < 256u; i += T) c2tab[i] = code2[i];
+    Strips st{};
+    st.c2tab = c2tab;
+#pragma unroll
+    for (int wt = 0; wt < W; ++wt) {
+        st.packed[wt] = A.packed[wt] + (int64_t)ex * A.packed_stride[wt];
+        st.a1[wt] = SM == kScaleBnb ? A.a1[wt] + (int64_t)ex * A.nb_stride[wt] : nullptr;
+        st.a2[wt] = A.a2[wt] + (int64_t)ex * A.n2_stride[wt];
+        st.sh2[wt] = A.sh2[wt];
+        if constexpr (SM == kScaleBnb) {
+            const float* code2 = A.code2[wt] + (int64_t)ex * A.code2_stride[wt];
+            for (uint32_t i = tid; i < 256u; i += T) c2tab[256u * wt + i] = code2[i];
+        }
+        if constexpr (W == 2) st.off[wt] = load_offset<SM>(A.offset[wt] ? A.offset[wt] + ex : nullptr);
     }
     write_lut(lut);
-    const float off = load_offset<SM>(A.offset ? A.offset + ex : nullptr);
+    if constexpr (W == 1) st.off[0] = load_offset<SM>(A.offset[0] ? A.offset[0] + ex : nullptr);
     __syncthreads();  // the pair list, ahead of the first gather
 
     // Loads run ahead of the MFMAs in registers, slots compile-time, chunk numbers past the
@@ -245,18 +315,25 @@ __global__ __launch_bounds__(64 * WV, MT <= 2 ? 2 : 1) void nf4_gemm_moe_kernel(
             }
         }
     };
+    // r: the strip's weight row, f: its 64-block on the expert's flat stream.  W = 2: one row and
+    // one block for both strips, ahead of the loads; W = 1: a row per strip, the block behind the
+    // packed load -- where the two kernels this template was merged from had them, which is what
+    // their instruction streams were measured with.
     auto wload = [&](auto S, uint32_t c) {
+        uint32_t r = col0 + nl, f = 0;
+        if constexpr (W == 2) f = r * bpr + 2u * c + (kh >> 1);
 #pragma unroll
         for (int nt = 0; nt < kMtStrips; ++nt) {
-            const uint32_t r = col0 + 16u * nt + nl;
-            w[S].w[nt] = *reinterpret_cast<const u32x4*>(packed + (r * kb + c * 64u + 16u * kh));  // < 2^31: validated
-            const uint32_t f = r * bpr + 2u * c + (kh >> 1);  // 64-block on the expert's flat stream
+            const int wt = Strips::wt(nt);
+            if constexpr (W == 1) r = col0 + 16u * nt + nl;
+            w[S].w[nt] = *reinterpret_cast<const u32x4*>(st.packed[wt] + (r * kb + c * 64u + 16u * kh));  // < 2^31: validated
+            if constexpr (W == 1) f = r * bpr + 2u * c + (kh >> 1);
             if constexpr (SM == kScaleBnb) {
-                w[S].qa[nt] = a1[f];
-                w[S].qb[nt] = a2[f >> A.sh2];
+                w[S].qa[nt] = st.a1[wt][f];
+                w[S].qb[nt] = st.a2[wt][f >> st.sh2[wt]];
             } else {
                 w[S].qa[nt] = 0u;
-                w[S].qb[nt] = a2[f];
+                w[S].qb[nt] = st.a2[wt][f];
             }
         }
     };
@@ -295,7 +372,7 @@ __global__ __launch_bounds__(64 * WV, MT <= 2 ? 2 : 1) void nf4_gemm_moe_kernel(
         const MtW& cur = w[j];
         float sc[kMtStrips];
 #pragma unroll
-        for (int nt = 0; nt < kMtStrips; ++nt) sc[nt] = block_scale<SM>(c2tab, cur.qa[nt], cur.qb[nt], off);
+        for (int nt = 0; nt < kMtStrips; ++nt) sc[nt] = block_scale<SM>(c2tab + 256 * Strips::wt(nt), cur.qa[nt], cur.qb[nt], st.off[Strips::wt(nt)]);
         auto aread = [&](u32x4(&a)[MT], int s) {
             const uint32_t slot = ((4u * kh + (uint32_t)s + rot) & 15u) * 16u;
 #pragma unroll
@@ -347,23 +424,21 @@ __global__ __launch_bounds__(64 * WV, MT <= 2 ? 2 : 1) void nf4_gemm_moe_kernel(
         step(std::integral_constant<int, 3>{}, i + 3u);
     }
 
-    // acc[mt][nt][i] = y[pair of staged row 16 mt + 4 kh + i][col0 + 16 nt + nl]
+    // acc[mt][nt][i]: strip nt's sum for the pair of staged row 16 mt + 4 kh + i -- W = 1:
+    // y[pair][col0 + 16 nt + nl]; W = 2: g (nt 0) and u (nt 1) of h[pair][col0 + nl]
     if (A.ksplit == 1u) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const uint32_t m = 16u * mt + 4u * kh + (uint32_t)i;
-                if (m < cnt) {
-                    const uint32_t at = prow[m] * A.N + col0 + nl;
-#pragma unroll
-                    for (int nt = 0; nt < kMtStrips; ++nt) store_y<DT>(A.y, at + 16u * nt, acc[mt][nt][i]);
-                }
+                if (m < cnt) Out::store(A.y, prow[m] * A.N + col0, nl, acc[mt][0][i], acc[mt][1][i]);
             }
         arrive();
         return;
     }
-    float* mine = A.slab + (size_t)ks * A.P * A.N;
+    const uint32_t plane = A.P * A.N;  // floats per plane; every slice's planes < 2^30 floats: validated
+    float* mine = A.slab + (W == 2 ? (size_t)ks * Out::kPlanes * plane : (size_t)ks * A.P * A.N);
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -372,14 +447,14 @@ __global__ __launch_bounds__(64 * WV, MT <= 2 ? 2 : 1) void nf4_gemm_moe_kernel(
             if (m < cnt) {
                 const uint32_t at = prow[m] * A.N + col0 + nl;
 #pragma unroll
-                for (int nt = 0; nt < kMtStrips; ++nt) mine[at + 16u * nt] = acc[mt][nt][i];
+                for (int nt = 0; nt < kMtStrips; ++nt) mine[at + Out::slab_at(nt, plane)] = acc[mt][nt][i];
             }
         }
     // publish, ticket, acquire and the slice-order reducer: the family's (nf4_gemm_mt_dev.h), with
     // the rows taken from the pair list and the ticket of this (expert, column tile)
     const MtJob job{A.x, A.y, A.slab, A.counters + et, smem, lut, flag, A.P, A.N, A.K, tile, ks, A.ksplit, A.cps, A.chunks};
     if (mt_publish_last(job.ticket, A.ksplit, flag)) {
-        mt_reduce<DT, MT, WV, MtStrips<1>, MtSumOut<DT>>(job, MtListedRows{cnt, prow});
+        mt_reduce<DT, MT, WV, Strips, Out>(job, MtListedRows{cnt, prow});
         arrive();
     }
 }

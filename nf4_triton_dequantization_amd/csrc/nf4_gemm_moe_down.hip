@@ -14,31 +14,8 @@ int launch_down(const nf4gemm::DownCall& a, const nf4_gemm_cfg& cfg, hipStream_t
     const MoePlan p = down_plan(cfg, m.P, e.experts, e.N, e.K);
     char* ws = reinterpret_cast<char*>(m.workspace);
     MoeDownArgs D{};
-    MoeArgs& A = D.g;
-    A.packed = e.packed;
-    A.a1 = e.absmax_q;
-    A.a2 = e.absmax2;
-    A.code2 = e.code2;
-    A.offset = e.offset;
-    A.ids = reinterpret_cast<const int32_t*>(m.ids);
-    A.x = m.x;
-    A.y = ws + down_scratch_offset(m.P, e.N, cfg);  // the products go to the scratch
-    A.counters = mt_counters(m.workspace);
-    A.slab = mt_slab(m.workspace, cfg);
-    A.packed_stride = e.packed_stride;
-    A.nb_stride = e.nb_stride;
-    A.n2_stride = e.n2_stride;
-    A.code2_stride = e.code2_stride;
-    A.P = (uint32_t)m.P;
-    A.E = (uint32_t)e.experts;
-    A.N = (uint32_t)e.N;
-    A.K = (uint32_t)e.K;
-    A.x_div = (uint32_t)m.x_div;
-    A.tiles = p.tiles;
-    A.ksplit = (uint32_t)cfg.ksplit;
-    A.cps = p.cps;
-    A.chunks = p.chunks;
-    A.sh2 = mt_log2_blocksize2(e.single, e.blocksize2);
+    D.g = moe_fill<1>(m, ws + down_scratch_offset(m.P, e.N, cfg), p, cfg);  // the products go to the scratch
+    const MoeArgsT<1>& A = D.g;
     D.c = MoeCombine{A.ids, a.rw, reinterpret_cast<const uint16_t*>(A.y), m.y, A.counters + p.tickets,
                      A.P, A.E, A.N, (uint32_t)a.topk, a.rw_dtype == NF4DQ_F32 ? 1u : 0u};
     int rc = NF4DQ_ERR_ARG;

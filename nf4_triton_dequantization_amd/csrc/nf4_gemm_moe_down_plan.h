@@ -51,7 +51,7 @@ inline size_t down_slab_bytes(int64_t P, int64_t N, const nf4_gemm_cfg& c) {
 }
 inline size_t down_scratch_offset(int64_t P, int64_t N, const nf4_gemm_cfg& c) { return kHeaderBytes + down_slab_bytes(P, N, c); }
 inline size_t down_workspace_need(int64_t P, int64_t N, int64_t K, const nf4_gemm_cfg& c) {
-    if (P < 1 || P > NF4DQ_MOE_MAX_PAIRS || N < 64 || N % 64 || K < (int64_t)kChunkK || K % kChunkK) return 0;
+    if (!mt_entry_shape(kMoeEntry, P, N, K)) return 0;
     return down_scratch_offset(P, N, c) + (size_t)P * (size_t)N * 2u;
 }
 

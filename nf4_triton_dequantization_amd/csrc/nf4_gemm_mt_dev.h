@@ -1,13 +1,13 @@
 // nf4_gemm_mt_dev.h -- the device pipeline of the row-tiled fused NF4 dequant + GEMM family in
 // bitsandbytes semantics, once.  nf4_gemm_mt.hip (33..128 dense rows) and nf4_gemm_mt_swiglu.hip
 // (gate/up with the SwiGLU chain behind them) are this pipeline under two sets of compile-time
-// policies.  nf4_gemm_moe_dev.h (one expert's listed rows: the kernel of nf4_gemm_moe.hip and, with the
-// routed sum behind it, of nf4_gemm_moe_down.hip) shares the ring entry, the rotation, the
-// decode, the MFMA call, the split-K hand-off and the reducer, and keeps its own chunk loop: its
-// row-tile guards are run-time, and built from the shared loop it did not keep the registers,
-// spills and speed it had (profiles/gemm_mt_family/README.md).  nf4_gemm_moe_swiglu.hip (one
-// expert's listed rows, gate and up with the SwiGLU chain) is that loop over MtStrips<2>, its own
-// copy for the same reason, with the hand-off, the reducer and the chain from here.
+// policies.  nf4_gemm_moe_dev.h (one expert's listed rows: the one kernel template of
+// nf4_gemm_moe.hip, of nf4_gemm_moe_down.hip with the routed sum behind it, and of
+// nf4_gemm_moe_swiglu.hip over MtStrips<2> with the SwiGLU chain) shares the ring entry, the
+// rotation, the decode, the MFMA call, the strip and output policies, the split-K hand-off and
+// the reducer, and keeps its own chunk loop: its row-tile guards are run-time, and built from the
+// shared loop it did not keep the registers, spills and speed it had
+// (profiles/gemm_mt_family/README.md).
 //
 // y[M][N] = x[M][K] . W[N][K]^T with W the 16-bit weights nf4_dequant_bnb writes, bit for
 // bit.  The families of nf4_gemm_dev.h hold x whole (LDS or registers) and at most two row

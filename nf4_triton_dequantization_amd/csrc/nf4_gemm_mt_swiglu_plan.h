@@ -20,21 +20,13 @@ namespace nf4gemm {
 
 constexpr uint32_t kSgTableBytes = 2 * 1024 + 64 + 16;  // behind the x buffers: two code2 tables, the NF4 codes, the reducer flag
 
-inline uint32_t sg_cols(const nf4_gemm_cfg& c) { return 16u * (uint32_t)c.waves; }
-// Dynamic LDS: the row-tiled layout with a second code2 table.
-inline uint32_t sg_lds_bytes(int64_t M) { return 2u * mt_xbuf_bytes(M) + kSgTableBytes; }
-
-// cfg fields: kernel = NF4DQ_GEMM_MT_SWIGLU; waves = waves per workgroup (2 / 4: 32 / 64 columns
-// of h); depth = K stage in 128-deep chunks (1); ksplit = K slices (1 .. min(K / 128, 16));
-// strips = 16-row weight strips per wave (2: one of gate, one of up; 0 = 2).
-inline bool valid_sg_cfg(const nf4_gemm_cfg& c, int64_t M, int64_t I, int64_t K) {
-    if (c.kernel != NF4DQ_GEMM_MT_SWIGLU || M < 1 || M > NF4DQ_GEMM_MT_MAX_M || I < 64 || K < (int64_t)kChunkK) return false;
-    if (c.waves != 2 && c.waves != 4) return false;
-    if (c.depth != 1 || (c.strips != 0 && c.strips != kMtStrips)) return false;
-    if (I % sg_cols(c)) return false;
-    if (c.ksplit < 1 || c.ksplit > kMtKsplitMax || c.ksplit > K / kChunkK) return false;
-    return sg_lds_bytes(M) <= kLdsPerCu;
-}
+// The row-tiled family's rules (nf4_gemm_mt_plan.h) over 16 columns of h per wave (32 / 64 a
+// workgroup), two planes per slice -- [ksplit][2][M][I]: the gate plane and the up plane -- and
+// the row-tiled LDS layout with a second code2 table.
+constexpr MtEntry kSgEntry{NF4DQ_GEMM_MT_SWIGLU, NF4DQ_GEMM_MT_MAX_M, 16u, 2, kSgTableBytes};
+inline uint32_t sg_cols(const nf4_gemm_cfg& c) { return mt_entry_cols(kSgEntry, c); }
+inline uint32_t sg_lds_bytes(int64_t M) { return mt_entry_lds(kSgEntry, M); }
+inline bool valid_sg_cfg(const nf4_gemm_cfg& c, int64_t M, int64_t I, int64_t K) { return mt_entry_valid(kSgEntry, c, M, I, K); }
 
 // The library's choice: mt_default_cfg's rule over this launch's column tiles -- four waves
 // (64 columns of h, 128 weight rows: I % 64 == 0 always allows them) and as many K slices as
@@ -49,34 +41,12 @@ inline bool valid_sg_cfg(const nf4_gemm_cfg& c, int64_t M, int64_t I, int64_t K)
 inline nf4_gemm_cfg sg_default_cfg(int64_t M, int64_t I, int64_t K, int cus) {
     (void)M;
     nf4_gemm_cfg c{NF4DQ_GEMM_MT_SWIGLU, 4, 1, 1, kMtStrips};
-    const int64_t tiles = I / sg_cols(c), chunks = K / kChunkK;
-    int64_t ks = tiles > 0 ? cus / tiles : 1;
-    if (ks > kMtKsplitMax) ks = kMtKsplitMax;
-    if (ks > chunks / kMtSliceChunks) ks = chunks / kMtSliceChunks;
-    c.ksplit = ks < 1 ? 1 : (int)ks;
+    c.ksplit = mt_entry_ksplit(cus, I / sg_cols(c), K);
     return c;
 }
-
-// Launch geometry: grid = column tiles x K slices (slice = block % ksplit), cps chunks per slice
-// (the last slices may be short or empty: they hand in zeros).
-inline MtPlan sg_plan(const nf4_gemm_cfg& c, int64_t M, int64_t I, int64_t K) {
-    MtPlan p{};
-    p.tiles = (uint32_t)(I / sg_cols(c));
-    p.chunks = (uint32_t)(K / kChunkK);
-    p.cps = (p.chunks + (uint32_t)c.ksplit - 1) / (uint32_t)c.ksplit;
-    p.row_tiles = (uint32_t)mt_row_tiles(M);
-    p.grid = p.tiles * (uint32_t)c.ksplit;
-    p.block = 64u * (uint32_t)c.waves;
-    p.dyn = sg_lds_bytes(M);
-    return p;
-}
-
-// Workspace: the row-tiled family's layout and contract -- the header (one ticket per column
-// tile) and, per K slice, the gate plane and the up plane of M * I floats each, all 0 between
-// calls.  Nothing for one slice, nothing for a shape the entry rejects.
+inline MtPlan sg_plan(const nf4_gemm_cfg& c, int64_t M, int64_t I, int64_t K) { return mt_entry_plan(kSgEntry, c, M, I, K, 1); }
 inline size_t sg_workspace_need(int64_t M, int64_t I, int64_t K, const nf4_gemm_cfg& c) {
-    if (M < 1 || M > NF4DQ_GEMM_MT_MAX_M || I < 64 || I % 64 || K < (int64_t)kChunkK || K % kChunkK) return 0;
-    return c.ksplit > 1 ? kHeaderBytes + (size_t)c.ksplit * 2u * (size_t)M * (size_t)I * 4u : 0;
+    return mt_entry_workspace(kSgEntry, M, I, K, c);
 }
 
 // One call of nf4_gemm_bnb_mt_swiglu: mats[0] is the gate weight, mats[1] the up weight.
@@ -112,8 +82,7 @@ inline int sg_check(const SgCall& a, int cus, nf4_gemm_cfg* out) {
     if (a.mats[0].blocksize != 64 || a.mats[1].blocksize != 64) return NF4DQ_ERR_SHAPE;  // larger statistics blocks: the composite
     const int64_t I = a.mats[0].N;
     if (a.mats[1].N != I) return NF4DQ_ERR_SHAPE;
-    if (a.M < 1 || a.M > NF4DQ_GEMM_MT_MAX_M || I < 64 || I % 64 || a.K < (int64_t)kChunkK || a.K % kChunkK)
-        return NF4DQ_ERR_SHAPE;
+    if (!mt_entry_shape(kSgEntry, a.M, I, a.K)) return NF4DQ_ERR_SHAPE;
     if (I > (int64_t(1) << 18) || a.K > (int64_t(1) << 24)) return NF4DQ_ERR_TOO_LARGE;
     const int64_t nblk = I * a.K / 64;
     for (int i = 0; i < 2; ++i) {
@@ -123,15 +92,7 @@ inline int sg_check(const SgCall& a, int cus, nf4_gemm_cfg* out) {
         if (a.single ? m.n2 < nblk : (m.nb < nblk || m.n2 < (nblk + m.blocksize2 - 1) / m.blocksize2)) return NF4DQ_ERR_SHAPE;
     }
     if (a.M * a.K * 2 >= (int64_t(1) << 31)) return NF4DQ_ERR_TOO_LARGE;
-    nf4_gemm_cfg c = a.cfg ? *a.cfg : sg_default_cfg(a.M, I, a.K, cus);
-    if (a.cfg && c.kernel == 0) c.kernel = NF4DQ_GEMM_MT_SWIGLU;
-    if (c.strips == 0) c.strips = kMtStrips;
-    if (!valid_sg_cfg(c, a.M, I, a.K)) return NF4DQ_ERR_ARG;
-    const size_t need = sg_workspace_need(a.M, I, a.K, c);
-    if (need >= (size_t(1) << 32)) return NF4DQ_ERR_TOO_LARGE;  // plane entries are indexed with 32 bits
-    if (need && (!a.workspace || a.workspace_bytes < need || !mt_aligned(a.workspace, 16))) return NF4DQ_ERR_ARG;
-    *out = c;
-    return NF4DQ_OK;
+    return mt_entry_resolve(kSgEntry, a.cfg, sg_default_cfg(a.M, I, a.K, cus), a.M, I, a.K, 0, a.workspace, a.workspace_bytes, out);
 }
 
 }  // namespace nf4gemm

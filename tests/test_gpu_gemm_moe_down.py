@@ -133,6 +133,26 @@ def test_every_routing_and_cfg_is_the_chain_of_the_expert_gemm(coracle, gpu, dt,
                 assert (got[0] == 0).all(), "a token whose ids are all invalid must be a row of +0 bits"
 
 
+@pytest.mark.parametrize("ksplit", [1, 2])
+@pytest.mark.parametrize("P", [16, 48, 80, 128])
+@pytest.mark.parametrize("waves", [2, 4])
+@pytest.mark.parametrize("mode", ["nested", "single"])
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+def test_every_instantiation(coracle, gpu, dt, mode, waves, P, ksplit):
+    """K = 640 (five chunks: one slice wraps the weight ring, two get 3 + 2), 2 / 4 / 6 / 8 row tiles,
+    k = 2, fp32 routing weights.  All pairs go to expert 1 but the last, which goes to expert 0: one
+    workgroup runs the instantiation with all its row tiles live, another with one, and two experts
+    arrive idle at every tile's ticket."""
+    K, k = 640, 2
+    S = _stack(coracle, gpu, mode, "drawn", E, N, K, dt)
+    ids = np.ones(P, np.int32)
+    ids[-1] = 0
+    xd = _x(P, K, dt)[0].to(gpu)
+    rw = _weights(P, seed=P)
+    cfg = (waves, ksplit)
+    _same(_down(S, xd, ids, 1, k, rw, cfg), _want(S, xd, ids, 1, k, rw, cfg), f"{dt} {mode} waves={waves} P={P} ksplit={ksplit}")
+
+
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
 @pytest.mark.parametrize("mode", ["nested", "single"])
 def test_weight_dtypes_special_values_statistics_and_shared_rows(coracle, gpu, dt, mode):

@@ -13,10 +13,12 @@ build are replayed in turn, ``rounds`` times.  ``grouped``: nf4_gemm_ref_grouped
 Llama q/k/v (4096, 1024, 1024) and gate/up (14336, 14336) groups at K = 4096.  One JSON line
 per point: per-launch medians, B over A, and the largest per-round deviation of A against its
 second copy.  ``nf4_gemm_bnb_mt`` and ``nf4_gemm_bnb_mt_swiglu`` (``--shapes`` are N,K and I,K)
-run over ``--ms``; ``nf4_gemm_bnb_moe`` over ``--moe`` ("experts,N,K,x_div;...") and ``--tokens``
-(two choices per token, drawn once).  All with the library's own cfg and the workspace each
-build asks for.  Before a point is timed every build runs it once on the same inputs into its
-own output.  For the three row-tiled entries any bit that differs from build A's ends the run:
+run over ``--ms``; the expert entries ``nf4_gemm_bnb_moe``, ``nf4_gemm_bnb_moe_swiglu`` (N = I, a
+gate and an up stack) and ``nf4_gemm_bnb_moe_down`` (top-2, fp32 routing weights) over ``--moe``
+("experts,N,K,x_div;...") and ``--tokens`` (two choices per token, drawn once).  All with the
+library's own cfg and the workspace each build asks for.  Before a point is timed every build
+runs it once on the same inputs into its own output.  For the row-tiled family's entries (those
+five) any bit that differs from build A's ends the run:
 their sums run in MFMA order over the chunks and in slice order in the reducer in every build,
 so anything but equality is a behaviour change.  For the older entries, whose builds may
 legitimately order a sum differently, the line only reports ``bit_equal``.
@@ -39,7 +41,9 @@ from tools.bench_gemm import _interleaved_rounds  # noqa: E402
 ENTRIES = ("nf4_gemm_ref", "nf4_gemm_ref_grouped", "nf4_gemm_bnb", "nf4_gemm_workspace_bytes",
            "nf4_gemm_grouped_workspace_bytes", "nf4_gemm_bnb_workspace_bytes", "nf4_gemm_check_workspace",
            "nf4_gemm_bnb_mt", "nf4_gemm_bnb_mt_workspace_bytes", "nf4_gemm_bnb_mt_swiglu",
-           "nf4_gemm_bnb_mt_swiglu_workspace_bytes", "nf4_gemm_bnb_moe", "nf4_gemm_bnb_moe_workspace_bytes")
+           "nf4_gemm_bnb_mt_swiglu_workspace_bytes", "nf4_gemm_bnb_moe", "nf4_gemm_bnb_moe_workspace_bytes",
+           "nf4_gemm_bnb_moe_swiglu", "nf4_gemm_bnb_moe_swiglu_workspace_bytes", "nf4_gemm_bnb_moe_down",
+           "nf4_gemm_bnb_moe_down_workspace_bytes")
 
 
 def load(name):
@@ -81,7 +85,7 @@ def main():
     code2 = torch.linspace(-1.0, 1.0, 256, device=dev)
     off = torch.full((1,), 0.01, device=dev)
 
-    EXACT = ("nf4_gemm_bnb_mt", "nf4_gemm_bnb_mt_swiglu", "nf4_gemm_bnb_moe")
+    EXACT = ("nf4_gemm_bnb_mt", "nf4_gemm_bnb_mt_swiglu", "nf4_gemm_bnb_moe", "nf4_gemm_bnb_moe_swiglu", "nf4_gemm_bnb_moe_down")
 
     def report(entry, what, M, n, ts, bit_equal):
         med = [sorted(t)[len(t) // 2] for t in ts]
@@ -169,27 +173,40 @@ def main():
 
                 point("nf4_gemm_bnb_mt_swiglu", f"{n}x{k}", M, copies, work, wsz, [sg(L, h) for L, h in zip(libs, hs)], hs)
             del ws, pairs
-    if "nf4_gemm_bnb_moe" in entries:
-        for E, n, k, x_div in [tuple(int(v) for v in s.split(",")) for s in args.moe.split(";") if s]:
-            copies = max(8, args.budget_mb * (1 << 20) // (E * n * k // 2))
-            nb, n2 = n * k // 64, (n * k // 64 + 255) // 256
-            stacks = []
-            for _ in range(copies):
-                q = torch.randint(0, 256, (E, n * k // 2), dtype=torch.uint8, device=dev, generator=gen)
-                a1 = torch.randint(0, 256, (E, nb), dtype=torch.uint8, device=dev, generator=gen)
-                a2 = torch.rand((E, n2), device=dev, generator=gen) * 0.01 + 1e-3
-                offs = torch.linspace(0.01, 0.02, E, device=dev)
-                d = _lib.MoeExperts(q.data_ptr(), n * k // 2, a1.data_ptr(), nb, code2.data_ptr(), 0, a2.data_ptr(), n2,
-                                    offs.data_ptr(), n, k, E, 0, 64, 256)
-                stacks.append((d, (q, a1, a2, offs)))
-            for tokens in [int(v) for v in args.tokens.split(",")]:
-                P = 2 * tokens  # two choices per token: w1 (x_div 2) reads the token's row twice, w2 a row per pair
-                ids = torch.randint(0, E, (P,), dtype=torch.int32, device=dev, generator=gen)
-                x = (torch.randn((-(-P // x_div), k), device=dev, generator=gen) * 0.05).to(torch.bfloat16)
+    moe_entries = [e for e in ("nf4_gemm_bnb_moe", "nf4_gemm_bnb_moe_swiglu", "nf4_gemm_bnb_moe_down") if e in entries]
+    for E, n, k, x_div in [tuple(int(v) for v in s.split(",")) for s in args.moe.split(";") if s] if moe_entries else ():
+        copies = max(8, args.budget_mb * (1 << 20) // (E * n * k // 2))
+        nb, n2 = n * k // 64, (n * k // 64 + 255) // 256
+
+        def stack(c2, lo):
+            q = torch.randint(0, 256, (E, n * k // 2), dtype=torch.uint8, device=dev, generator=gen)
+            a1 = torch.randint(0, 256, (E, nb), dtype=torch.uint8, device=dev, generator=gen)
+            a2 = torch.rand((E, n2), device=dev, generator=gen) * 0.01 + 1e-3
+            offs = torch.linspace(lo, 2 * lo, E, device=dev)
+            d = _lib.MoeExperts(q.data_ptr(), n * k // 2, a1.data_ptr(), nb, c2.data_ptr(), 0, a2.data_ptr(), n2,
+                                offs.data_ptr(), n, k, E, 0, 64, 256)
+            return d, (q, a1, a2, offs)
+
+        stacks = [stack(code2, 0.01) for _ in range(copies)]
+        what = f"{E}x{n}x{k} x_div={x_div}"
+        gate_up = []
+        if "nf4_gemm_bnb_moe_swiglu" in entries:  # the stacks above are the gates; an up stack each
+            code2u = torch.linspace(0.75, -0.75, 256, device=dev)
+            ups = [stack(code2u, -0.02) for _ in range(copies)]
+            gate_up = [(_lib.MoeExperts * 2)(g[0], u[0]) for g, u in zip(stacks, ups)]
+        for tokens in [int(v) for v in args.tokens.split(",")]:
+            P = 2 * tokens  # two choices per token: w1 (x_div 2) reads the token's row twice, w2 a row per pair
+            ids = torch.randint(0, E, (P,), dtype=torch.int32, device=dev, generator=gen)
+            x = (torch.randn((-(-P // x_div), k), device=dev, generator=gen) * 0.05).to(torch.bfloat16)
+            first = ctypes.cast(ctypes.pointer(stacks[0][0]), ctypes.c_void_p)
+
+            def workspace(bytes_entry, desc):
+                wsz = max(getattr(L, bytes_entry)(P, desc, None) for L in libs)
+                return torch.zeros(max(wsz, 1 << 17), dtype=torch.uint8, device=dev), wsz
+
+            if "nf4_gemm_bnb_moe" in entries:
                 ys = bf16_out(P, n)
-                wsz = max(L.nf4_gemm_bnb_moe_workspace_bytes(P, ctypes.cast(ctypes.pointer(stacks[0][0]), ctypes.c_void_p), None)
-                          for L in libs)
-                work = torch.zeros(max(wsz, 1 << 17), dtype=torch.uint8, device=dev)
+                work, wsz = workspace("nf4_gemm_bnb_moe_workspace_bytes", first)
 
                 def moe(L, y):
                     def run():
@@ -200,9 +217,38 @@ def main():
                             assert rc == 0, rc
                     return run
 
-                point("nf4_gemm_bnb_moe", f"{E}x{n}x{k} x_div={x_div}", P, copies, work, wsz,
-                      [moe(L, y) for L, y in zip(libs, ys)], ys)
-            del stacks
+                point("nf4_gemm_bnb_moe", what, P, copies, work, wsz, [moe(L, y) for L, y in zip(libs, ys)], ys)
+            if "nf4_gemm_bnb_moe_swiglu" in entries:
+                hs = bf16_out(P, n)
+                work, wsz = workspace("nf4_gemm_bnb_moe_swiglu_workspace_bytes", ctypes.cast(gate_up[0], ctypes.c_void_p))
+
+                def msg(L, h):
+                    def run():
+                        sp = torch.cuda.current_stream().cuda_stream
+                        for gu in gate_up:
+                            rc = L.nf4_gemm_bnb_moe_swiglu(x.data_ptr(), ids.data_ptr(), P, x_div, ctypes.cast(gu, ctypes.c_void_p),
+                                                           _lib.ACT_SILU, h.data_ptr(), _lib.BF16, work.data_ptr(), work.numel(), None, sp)
+                            assert rc == 0, rc
+                    return run
+
+                point("nf4_gemm_bnb_moe_swiglu", what, P, copies, work, wsz, [msg(L, h) for L, h in zip(libs, hs)], hs)
+            if "nf4_gemm_bnb_moe_down" in entries:
+                rw = torch.rand(P, device=dev, generator=gen) * 0.96 + 0.02
+                ys = bf16_out(tokens, n)
+                work, wsz = workspace("nf4_gemm_bnb_moe_down_workspace_bytes", first)
+
+                def down(L, y):
+                    def run():
+                        sp = torch.cuda.current_stream().cuda_stream
+                        for d, _ in stacks:
+                            rc = L.nf4_gemm_bnb_moe_down(x.data_ptr(), ids.data_ptr(), P, x_div, 2, rw.data_ptr(), _lib.F32,
+                                                         ctypes.cast(ctypes.pointer(d), ctypes.c_void_p), y.data_ptr(), _lib.BF16,
+                                                         work.data_ptr(), work.numel(), None, sp)
+                            assert rc == 0, rc
+                    return run
+
+                point("nf4_gemm_bnb_moe_down", what, P, copies, work, wsz, [down(L, y) for L, y in zip(libs, ys)], ys)
+        del stacks, gate_up
     for n, k in shapes if ("nf4_gemm_ref" in entries or "nf4_gemm_bnb" in entries) else ():
         copies = max(8, args.budget_mb * (1 << 20) // (n * k // 2))
         ws = [weight(n, k) for _ in range(copies)]

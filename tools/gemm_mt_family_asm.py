@@ -38,12 +38,13 @@ def makefile_flags():
 
 
 FLAGS = makefile_flags()
-# source -> (profiles directory, kernel, bytes of tables behind the x buffers: the plan headers' k*TableBytes)
-FAMILY = {"nf4_gemm_mt": ("gemm_mt", "nf4_gemm_mt_kernel", 1104),
-          "nf4_gemm_mt_swiglu": ("gemm_mt_swiglu", "nf4_gemm_mt_swiglu_kernel", 2128),
-          "nf4_gemm_moe": ("gemm_moe", "nf4_gemm_moe_kernel", 2128),
-          "nf4_gemm_moe_swiglu": ("gemm_moe_swiglu", "nf4_gemm_moe_swiglu_kernel", 3152),
-          "nf4_gemm_moe_down": ("gemm_moe_down", "nf4_gemm_moe_kernel", 2128)}
+# source -> (profiles directory, the kernel template as the source instantiates it, bytes of tables behind
+# the x buffers: the plan headers' k*TableBytes)
+FAMILY = {"nf4_gemm_mt": ("gemm_mt", "nf4_gemm_mt_kernel<DT, MT, SM, WV>", 1104),
+          "nf4_gemm_mt_swiglu": ("gemm_mt_swiglu", "nf4_gemm_mt_swiglu_kernel<DT, MT, SM, WV>", 2128),
+          "nf4_gemm_moe": ("gemm_moe", "nf4_gemm_moe_kernel<DT, MT, SM, WV> (DOWN = false, W = 1)", 2128),
+          "nf4_gemm_moe_swiglu": ("gemm_moe_swiglu", "nf4_gemm_moe_kernel<DT, MT, SM, WV, false, 2> (W = 2: gate and up, SwiGLU)", 3152),
+          "nf4_gemm_moe_down": ("gemm_moe_down", "nf4_gemm_moe_kernel<DT, MT, SM, WV, true> (DOWN: the routed sum, W = 1)", 2128)}
 FIELDS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch",
           "Occupancy [waves/SIMD]": "waves", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill",
           "LDS Size [bytes/block]": "static_lds"}
@@ -98,7 +99,7 @@ def params(name):
 def write_table(out, src):
     prof, kernel, tables = FAMILY[src]
     ks = kernels(out, src)
-    rows = [f"{kernel}<DT, MT, SM, WV{', true' if src == 'nf4_gemm_moe_down' else ''}>: hipcc {' '.join(f for f in FLAGS if f not in ('-fPIC', '-Wall', '-S', '--cuda-device-only'))}",
+    rows = [f"{kernel}: hipcc {' '.join(f for f in FLAGS if f not in ('-fPIC', '-Wall', '-S', '--cuda-device-only'))}",
             f"(LDS is dynamic: two x buffers of 16 MT rows x 256 bytes + {tables} bytes behind them; static LDS 0."
             "  Columns: the compiler's remarks; SGPRs = TotalSGPRs; spills: SGPR + VGPR; LDS bytes: computed as the"
             " plan header does, not measured)", "",
