@@ -641,9 +641,15 @@ int nf4_gemm_bnb_moe_swiglu(const void* x, const void* expert_ids, int64_t P, in
  * Workspace (nf4_gemm_bnb_moe_down_workspace_bytes; never 0 for a valid call): the ticket header
  * -- experts * column tiles tickets of the K slices, then one ticket per column tile for the
  * combine; more than the header holds: NF4DQ_ERR_TOO_LARGE --, then ksplit slabs of P * N floats
- * when ksplit > 1, then P * N 16-bit products.  Header and slabs are zero between calls, as for
- * the other fused entries; the products are don't-care (every one read was written by the same
- * call).  Per column tile each expert arrives once, after its rows are stored (an expert without
+ * when ksplit > 1, then P * N 16-bit products.  The workspace is zero before its first use and is
+ * this entry's alone (another entry's slabs must be zero where this one leaves its products).  The
+ * header is zero after every call.  The products are don't-care: every one read was written by the
+ * same call.  The slabs are zero between calls of one (P, N, ksplit).  Where one workspace serves
+ * calls of different (P, N, ksplit), an earlier call's products may lie where a later call has its
+ * slabs: every slab element a reducer reads was stored by a slice of the same call, so the result
+ * is the same, and afterwards the slab rows of pairs with a valid id are zero, while those of
+ * pairs without one keep what lay there.
+ * Per column tile each expert arrives once, after its rows are stored (an expert without
  * a pair at once, with no weight or statistics traffic); the last arrival combines the tile.  No
  * workgroup waits for another, so the split-K error word is never set, and the result is a
  * function of the inputs and the cfg alone.

@@ -541,9 +541,11 @@ def _gemm_workspace(device: torch.device, nbytes: int) -> torch.Tensor:
 
 
 # nf4_moe_down_bnb's workspaces, apart from the shared ones: the launch leaves its 16-bit products
-# behind the slabs, where another entry's larger slabs would expect zeros.  Their tickets and
-# slabs are 0 between calls like the shared ones'; no workgroup of that launch waits for another,
-# so their error word is never set and check_gemm_workspaces() has nothing to read in them.
+# behind the slabs, where another entry's larger slabs would expect zeros.  Their tickets are 0
+# between calls like the shared ones'; a later call of another (P, N, ksplit) may find those
+# products in its own slabs, which it overwrites before it reads them (include/nf4_dequant.h).  No
+# workgroup of that launch waits for another, so their error word is never set and
+# check_gemm_workspaces() has nothing to read in them.
 _MOE_DOWN_WS = {}
 
 

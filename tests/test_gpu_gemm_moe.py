@@ -52,34 +52,44 @@ class _Stack:
     """E experts of one shape on the device, stacked with padded strides, and the oracle's 16-bit
     matrix [N, K] of each.  mode "nested": own a1 / a2 / offset and a code2 table per expert
     (code2_stride 256); "single": own fp32 absmax.  ``kind`` "sensitive": sensitive_weight_bnb
-    per expert (one code2 table shared by all: code2_stride 0)."""
+    per expert (one code2 table shared by all: code2_stride 0).  What the suites of this file fix
+    can be named (test_gpu_gemm_family_drawn.py draws it): ``bs2`` the blocksize2 of a drawn stack
+    (sensitive weights are built for 16), ``shared_code2`` one table for all experts (a drawn stack:
+    the dynamic map itself), ``null_offset`` every offset 0 and the descriptor's pointer NULL,
+    ``pads`` the bytes / bytes / floats by which packed_stride, nb_stride and n2_stride exceed the
+    data (the first a multiple of 16)."""
 
-    def __init__(self, coracle, gpu, mode, kind, E, N, K, dt):
+    def __init__(self, coracle, gpu, mode, kind, E, N, K, dt, bs2=None, shared_code2=None, null_offset=False,
+                 pads=(4096 + 16, 3, 1)):
         self.mode, self.E, self.N, self.K, self.dt, self.gpu = mode, E, N, K, dt, gpu
         nblk = N * K // 64
-        self.bs2 = BLOCKSIZE2 if kind == "sensitive" else 256
+        assert bs2 is None or kind != "sensitive"
+        self.bs2 = BLOCKSIZE2 if kind == "sensitive" else 256 if bs2 is None else bs2
         n2 = -(-nblk // self.bs2)
-        self.pstride, self.nbstride, self.n2stride = N * K // 2 + 4096 + 16, nblk + 3, (nblk if mode == "single" else n2) + 1
+        assert pads[0] % 16 == 0 and min(pads) >= 0
+        self.pstride, self.nbstride, self.n2stride = N * K // 2 + pads[0], nblk + pads[1], (nblk if mode == "single" else n2) + pads[2]
+        self.null_offset = null_offset and mode == "nested"
         packed = np.full((E, self.pstride), 0xFF, np.uint8)
         self.bits = []
         if mode == "nested":
             a1 = np.full((E, self.nbstride), 0xFF, np.uint8)
             a2 = np.full((E, self.n2stride), 1e30, np.float32)
-            self.shared_code2 = kind == "sensitive"
+            self.shared_code2 = kind == "sensitive" if shared_code2 is None else shared_code2
             code2 = np.zeros((1 if self.shared_code2 else E, 256), np.float32)
             offset = np.zeros(E, np.float32)
             for e in range(E):
                 if kind == "sensitive":
                     q, b1, c2, b2, off = sensitive_weight_bnb(N, K, dt, seed=e + 1)[:5]
                 else:
-                    q, b1, c2, b2, off = drawn_weight_bnb(N, K, seed=N + K + 7 * e)
-                    c2 = (c2 * np.float32(1.0 + 0.03 * e)).astype(np.float32)   # the expert's own table
+                    q, b1, c2, b2, off = drawn_weight_bnb(N, K, seed=N + K + 7 * e, blocksize2=self.bs2)
+                    if not self.shared_code2:
+                        c2 = (c2 * np.float32(1.0 + 0.03 * e)).astype(np.float32)   # the expert's own table
                     off = float(np.float32(off) + np.float32(0.004) * np.float32(e))  # ... and offset, none 0
                 packed[e, :q.size], a1[e, :nblk], a2[e, :n2] = q, b1, b2
-                code2[0 if self.shared_code2 else e], offset[e] = c2, off
+                code2[0 if self.shared_code2 else e], offset[e] = c2, 0.0 if self.null_offset else off
                 self.bits.append(coracle.dequant_bnb(q, b1, c2, b2, float(offset[e]), N * K, _code(dt), 64,
                                                      self.bs2).reshape(N, K))
-            assert kind == "sensitive" or (len(set(offset.tolist())) == E and (offset != 0).all())
+            assert kind == "sensitive" or self.null_offset or (len(set(offset.tolist())) == E and (offset != 0).all())
             self.t = [torch.from_numpy(v).to(gpu) for v in (packed, a1, code2, a2, offset)]
         else:
             am = np.full((E, self.n2stride), 1e30, np.float32)
@@ -99,7 +109,8 @@ class _Stack:
         if self.mode == "nested":
             q, a1, c2, a2, off = self.t
             return _lib.MoeExperts(q.data_ptr(), self.pstride, a1.data_ptr(), self.nbstride, c2.data_ptr(),
-                                   0 if self.shared_code2 else 256, a2.data_ptr(), self.n2stride, off.data_ptr(),
+                                   0 if self.shared_code2 else 256, a2.data_ptr(), self.n2stride,
+                                   None if self.null_offset else off.data_ptr(),
                                    self.N, self.K, self.E, 0, 64, self.bs2)
         q, am = self.t
         return _lib.MoeExperts(q.data_ptr(), self.pstride, None, 0, None, 0, am.data_ptr(), self.n2stride, None,

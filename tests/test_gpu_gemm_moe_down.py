@@ -18,7 +18,7 @@ import torch
 
 from _moe_down_cases import chain, rn16
 from test_gpu_gemm_moe import _cfg as _moe_cfg
-from test_gpu_gemm_moe import _lib_and_L, _moe, _stack, _tdt, _x
+from test_gpu_gemm_moe import _lib_and_L, _moe, _Stack, _stack, _tdt, _x
 
 pytestmark = pytest.mark.gpu
 
@@ -58,9 +58,10 @@ def _routings(P, k, seed):
     return pats
 
 
-def _down(S, xd, ids_np, x_div, k, rw, cfg=None, ws=None, fill=True):
+def _down(S, xd, ids_np, x_div, k, rw, cfg=None, ws=None, fill=True, slabs_zero=True):
     """One call of the entry.  rw: np.float32 values or np.uint16 patterns of the output dtype.
-    Returns y's bits [P / k, N]."""
+    Returns y's bits [P / k, N].  slabs_zero False: only the header is checked to read 0 afterwards
+    (a workspace that an earlier call of another layout left its products in)."""
     _lib, L = _lib_and_L()
     P, T = len(ids_np), len(ids_np) // k
     c = None if cfg is None else _lib.GemmCfg(MOE_DOWN, cfg[0], 1, cfg[1], 2)
@@ -89,7 +90,7 @@ def _down(S, xd, ids_np, x_div, k, rw, cfg=None, ws=None, fill=True):
                                  cp, sp)
     assert rc == 0, (cfg, _lib.strerror(rc))
     assert L.nf4_gemm_check_workspace(ws.data_ptr(), wsz, sp) == 0
-    assert int(ws[:scratch_at].count_nonzero()) == 0, f"tickets or slab entries left set, cfg {cfg}"
+    assert int(ws[:scratch_at if slabs_zero else HEADER].count_nonzero()) == 0, f"tickets or slab entries left set, cfg {cfg}"
     assert bool((buf[:BAND] == 0x5A5B).all()) and bool((buf[BAND + T:] == 0x5A5B).all()), f"band written, cfg {cfg}"
     return _bits(y)
 
@@ -216,6 +217,56 @@ def test_two_calls_on_one_workspace_without_a_memset(coracle, gpu, dt):
         _same(first, _want(S, xd, a, 1, k, rw, cfg), f"first call {dt} cfg {cfg}")
         _same(second, _want(S, xd, b, 1, k, rw, cfg), f"second call on the same workspace {dt} cfg {cfg}")
         _same(third, first, f"the first routing again {dt} cfg {cfg}")
+
+
+def test_an_earlier_layouts_products_in_a_later_calls_slabs(coracle, gpu):
+    """Found by the drawn sequence of test_gpu_gemm_family_drawn.py (seed 20260, moe_down / bf16, cases
+    0 and 3) and pinned here by its fields: ONE workspace, nothing cleared in between.
+    First 256 single-statistics experts of 64 x 128, 97 pairs, one K slice: the 16-bit products lie
+    right behind the header.  Then 17 nested experts of 64 x 1152 (one shared code2 table), 67 pairs,
+    2 waves x 8 K slices, ids outside 0..16 among valid ones: slab 0 begins where those products lie.
+    Every slab element the reducer reads was stored by a slice of the same call, so the second result
+    is the chain bit for bit; afterwards the header and the slab rows of valid pairs read 0, and the
+    rows of pairs without a valid id hold what lay there (include/nf4_dequant.h) -- in slab 0, rows
+    0 .. 47, the first call's products.  The first layout again, on the same workspace, gives its
+    first result."""
+    _lib, L = _lib_and_L()
+    dt, n = "bf16", 64
+    A = _Stack(coracle, gpu, "single", "drawn", 256, n, 128, dt, pads=(704, 2, 2))
+    B = _Stack(coracle, gpu, "nested", "drawn", 17, n, 1152, dt, bs2=256, shared_code2=True, pads=(2112, 6, 0))
+    (Pa, cfga), (Pb, cfgb) = (97, (2, 1)), (67, (2, 8))
+
+    def need(S, P, cfg):
+        d, c = S.desc(), _lib.GemmCfg(MOE_DOWN, cfg[0], 1, cfg[1], 2)
+        return L.nf4_gemm_bnb_moe_down_workspace_bytes(P, ctypes.cast(ctypes.pointer(d), ctypes.c_void_p), ctypes.byref(c))
+
+    wa, wb = need(A, Pa, cfga), need(B, Pb, cfgb)
+    assert wa == HEADER + Pa * n * 2 and wb == HEADER + 8 * Pb * n * 4 + Pb * n * 2
+    ws = torch.zeros(max(wa, wb), dtype=torch.uint8, device=gpu)
+    ids_a = np.arange(Pa) * 37 % 256                                  # every id valid: every product row is stored
+    ids_b = np.array([3, -1, 0, 17, 16, 5, 2 ** 31 - 1, 1, -2 ** 31, 18])[np.arange(Pb) % 10]
+    valid = (ids_b >= 0) & (ids_b < 17)
+    xa, xb = _x(Pa, 128, dt)[0].to(gpu), _x(Pb, 1152, dt)[0].to(gpu)
+    rwa, rwb = _weights(Pa, seed=21), _weights(Pb, seed=22)
+
+    first = _down(A, xa, ids_a, 1, 1, rwa, cfga, ws=ws[:wa])
+    _same(first, _want(A, xa, ids_a, 1, 1, rwa, cfga), "first layout")
+    slabs = ws[HEADER:wb - Pb * n * 2].view(torch.int32).view(8, Pb, n)   # the second call's slabs
+    before = slabs.clone()
+    stale = Pa * n * 2 // (n * 4)                                     # rows of slab 0 the products cover: 48 (and half of row 48)
+    assert stale == 48 and bool((before[0, :stale] != 0).any(dim=1).all()), "the first call's products are not where slab 0 begins"
+    assert int(before[1:].count_nonzero()) == 0
+
+    second = _down(B, xb, ids_b, 1, 1, rwb, cfgb, ws=ws[:wb], fill=False, slabs_zero=False)
+    _same(second, _want(B, xb, ids_b, 1, 1, rwb, cfgb), "second layout over the first one's products")
+    vt = torch.from_numpy(valid).to(gpu)
+    assert int(slabs[:, vt].count_nonzero()) == 0, "slab rows of valid pairs left set"
+    assert torch.equal(slabs[:, ~vt], before[:, ~vt]), "slab rows of pairs without a valid id were written"
+    assert (~valid[:stale]).sum() == 23 and bool((slabs[0, :stale][~vt[:stale]] != 0).any(dim=1).all()), \
+        "no stale products left in the rows of invalid ids: the case no longer has the property it pins"
+
+    third = _down(A, xa, ids_a, 1, 1, rwa, cfga, ws=ws[:wa], fill=False)
+    _same(third, first, "the first layout again")
 
 
 def test_argument_errors_launch_nothing(coracle, gpu):

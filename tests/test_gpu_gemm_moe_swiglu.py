@@ -54,29 +54,36 @@ def _bits(t):
 class _UpStack(MOE._Stack):
     """The up stack: as test_gpu_gemm_moe._Stack (whose ``desc`` it uses), but nested statistics
     have blocksize2 16 and ONE code2 table for all experts, the offsets are its own, and the padded
-    strides differ from the gate stack's."""
+    strides differ from the gate stack's.  ``bs2``, ``shared_code2`` (False: the shared table scaled
+    by 1 + 0.02 e per expert, code2_stride 256), ``null_offset`` and ``pads`` as in _Stack, for
+    test_gpu_gemm_family_drawn.py."""
 
-    def __init__(self, coracle, gpu, mode, E, N, K, dt):
+    def __init__(self, coracle, gpu, mode, E, N, K, dt, bs2=16, shared_code2=True, null_offset=False, pads=(2048 + 32, 5, 2)):
         self.mode, self.E, self.N, self.K, self.dt, self.gpu = mode, E, N, K, dt, gpu
         nblk = N * K // 64
-        self.bs2 = 16
+        self.bs2 = bs2
         n2 = -(-nblk // self.bs2)
-        self.pstride, self.nbstride, self.n2stride = N * K // 2 + 2048 + 32, nblk + 5, (nblk if mode == "single" else n2) + 2
+        assert pads[0] % 16 == 0 and min(pads) >= 0
+        self.pstride, self.nbstride, self.n2stride = N * K // 2 + pads[0], nblk + pads[1], (nblk if mode == "single" else n2) + pads[2]
+        self.null_offset = null_offset and mode == "nested"
         packed = np.full((E, self.pstride), 0xFF, np.uint8)
         self.bits = []
         if mode == "nested":
-            self.shared_code2 = True
+            self.shared_code2 = shared_code2
             a1 = np.full((E, self.nbstride), 0xFF, np.uint8)
             a2 = np.full((E, self.n2stride), 1e30, np.float32)
             code2 = (code2_np()[::-1] * np.float32(0.75)).astype(np.float32).reshape(1, 256).copy()
+            if not shared_code2:
+                code2 = (code2 * (np.float32(1.0) + np.float32(0.02) * np.arange(E, dtype=np.float32))[:, None]).astype(np.float32)
             offset = np.zeros(E, np.float32)
             for e in range(E):
-                q, b1, _, b2, _ = drawn_weight_bnb(N, K, seed=N + K + 3 + 7 * e, blocksize2=16)
+                q, b1, _, b2, _ = drawn_weight_bnb(N, K, seed=N + K + 3 + 7 * e, blocksize2=self.bs2)
                 packed[e, :q.size], a1[e, :nblk], a2[e, :n2] = q, b1, b2
-                offset[e] = np.float32(-0.0371) - np.float32(0.003) * np.float32(e)
-                self.bits.append(coracle.dequant_bnb(q, b1, code2[0], b2, float(offset[e]), N * K, _code(dt), 64,
-                                                     16).reshape(N, K))
-            assert len(set(offset.tolist())) == E and (offset != 0).all()
+                if not self.null_offset:
+                    offset[e] = np.float32(-0.0371) - np.float32(0.003) * np.float32(e)
+                self.bits.append(coracle.dequant_bnb(q, b1, code2[0 if shared_code2 else e], b2, float(offset[e]), N * K,
+                                                     _code(dt), 64, self.bs2).reshape(N, K))
+            assert self.null_offset or (len(set(offset.tolist())) == E and (offset != 0).all())
             self.t = [torch.from_numpy(v).to(gpu) for v in (packed, a1, code2, a2, offset)]
         else:
             am = np.full((E, self.n2stride), 1e30, np.float32)

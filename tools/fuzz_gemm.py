@@ -22,6 +22,13 @@ float weight with ``nf4_quantize`` (nested or plain fp32 statistics, blocksize 6
 ``--cfg-rate`` of the cases, a drawn configuration through ``nf4_gemm_bnb`` /
 ``nf4_gemm_bnb_single`` (a family without the mode is rejected and skipped); the oracle is
 the C oracle's ``dequant_bnb`` / ``dequant_bnb_single``, same tolerance.
+
+``--semantics family``: the row-tiled and the expert GEMM family (nf4_gemm_bnb_mt, _mt_swiglu, _moe,
+_moe_swiglu, _moe_down) on the drawn cases of tests/_family_draws.py, run and judged exactly as
+tests/test_gpu_gemm_family_drawn.py does (its ``Runner``: one workspace per (entry, dtype) sequence,
+every call twice, the suites' own judges).  Round r draws ``--seed`` + r for each of the ten
+(entry, dtype) sequences; ``--cases`` counts calls over all rounds.  One JSON line per failing case
+with its fields.
 """
 from __future__ import annotations
 
@@ -200,10 +207,46 @@ def bnb_case(rng, L, orc, dev, cfg_rate):
     return records, ran
 
 
+def family_sweep(args, orc, dev):
+    """--semantics family: rounds of the ten drawn sequences until --cases or --seconds is reached."""
+    import _family_draws as D
+    import test_gpu_gemm_family_drawn as T
+
+    t0 = time.time()
+    done = bad = stale = rounds = 0
+    per_entry = {e: 0 for e in D.ENTRIES}
+    while done < args.cases and time.time() - t0 <= args.seconds:
+        seed = args.seed + rounds
+        for entry in D.ENTRIES:
+            for dt in D.DTYPES:
+                cases = D.draws(entry, dt, seed)
+                runner = T.Runner(entry, dt, orc, dev)
+                runner.prepare(cases)
+                for c in cases:
+                    if done >= args.cases or time.time() - t0 > args.seconds:
+                        break
+                    try:
+                        runner.run(c)
+                    except AssertionError as e:
+                        bad += 1
+                        print(json.dumps({"mismatch": dict(c.fields(), semantics="family", error=str(e).split("\n", 1)[-1][:400])}),
+                              flush=True)
+                    done += 1
+                    per_entry[entry] += 1
+                stale += runner.stale_slab_calls
+                T._STACKS.clear()
+        rounds += 1
+        print(json.dumps({"progress": done, "mismatches": bad, "rounds": rounds, "seconds": round(time.time() - t0, 1)}), flush=True)
+    print(json.dumps({"summary": {"semantics": "family", "cases": done, "launches": 2 * done, "per_entry": per_entry,
+                                  "rounds": rounds, "mismatches": bad, "moe_down_calls_over_stale_products": stale,
+                                  "seed": args.seed, "seconds": round(time.time() - t0, 1)}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--semantics", choices=["ref", "bnb"], default="ref",
-                    help="ref: nf4_gemm_ref and its kin; bnb: nf4_gemm_bnb / nf4_gemm_bnb_single on nf4_quantize's weights")
+    ap.add_argument("--semantics", choices=["ref", "bnb", "family"], default="ref",
+                    help="ref: nf4_gemm_ref and its kin; bnb: nf4_gemm_bnb / nf4_gemm_bnb_single on nf4_quantize's weights; "
+                         "family: the row-tiled and expert GEMMs on the drawn cases of tests/_family_draws.py")
     ap.add_argument("--cases", type=int, default=1500)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--seconds", type=float, default=500.0)
@@ -217,6 +260,8 @@ def main():
     dev = torch.device("cuda", 0)
     L = _lib.lib()
     orc = O.COracle()
+    if args.semantics == "family":
+        return family_sweep(args, orc, dev)
     rng = np.random.default_rng(args.seed)
     t0 = time.time()
     done = bad = cfg_runs = grouped_runs = 0
