@@ -96,8 +96,9 @@ __global__ __launch_bounds__(64 * nf4lora::kMaxWaves) void nf4_lora_kernel(const
         // Every load is unconditional -- a lane past M or r reads row 0 and its fragment is zeroed
         // in registers -- and kU chunks are loaded per step, so that a step's loads are all in
         // flight before its first MFMA waits for one: the loop is bound by load latency, not by
-        // bytes.  A chunk past the wave's range is zeros, which add +0: the order of the sum stays
-        // c0, c0 + 1, ..
+        // bytes.  A chunk past the wave's range re-reads the last one and takes no part in the sum
+        // (not even as a zero operand: the x it re-read may hold an infinity, and inf * 0 is NaN):
+        // the order of the sum stays c0, c0 + 1, ..
         constexpr uint32_t kU = RT >= 8 ? 2 : 4;
         const u32x4 zero = {0, 0, 0, 0};
         const char* xp[MB];
@@ -128,11 +129,11 @@ __global__ __launch_bounds__(64 * nf4lora::kMaxWaves) void nf4_lora_kernel(const
             }
 #pragma unroll
             for (uint32_t h = 0; h < kU; ++h) {
-                const bool in = c + h < c1;
+                if (c + h >= c1) break;  // uniform over the wave
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) {
                     if ((uint32_t)rt < rtiles) {
-                        const u32x4 bq = in && ain[rt] ? af[h][rt] : zero;
+                        const u32x4 bq = ain[rt] ? af[h][rt] : zero;
 #pragma unroll
                         for (int mb = 0; mb < MB; ++mb) acc[mb][rt] = lora_mfma<DT>(xin[mb] ? xf[h][mb] : zero, bq, acc[mb][rt]);
                     }

@@ -4,7 +4,9 @@ the GEMM bound carried through it), under the library's plan and under every cfg
 ``base`` null, in place and a separate tensor -- all three under the library's plan at every shape,
 ONE of the three per explicit cfg, rotating with the cfg and the shape, so every (cfg, mode) pair
 meets every M, K, r and N several times but not every (shape, cfg, mode) triple is run --; a
-grouped call; the exact probes bit for bit; scale
+grouped call; the exact probes bit for bit; the rounding-chain probes of _lora_cases.py bit for bit
+(every one of the header's four roundings changes its value there, and the expected bits are unique),
+alone and three in one group; scale
 0, negative and with all mantissa bits; the same bits on every call.  Every output lies between
 sentinel bands that must stay untouched, and starts as NaN wherever the launch must write it."""
 import ctypes
@@ -14,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from _lora_cases import TDT, check, drawn_case, exact_case, lora_oracle
+from _lora_cases import TDT, check, drawn_case, exact_case, lora_oracle, rounding_case
 from nf4_triton_dequantization_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -34,10 +36,12 @@ assert np.float32(FULL_MANTISSA).view(np.uint32) == 0x3FFFFFFF
 class Case:
     """One shape's inputs on the device with its references, computed once and never changed."""
 
-    def __init__(self, gpu, M, K, r, N, dt, scale=1.5, seed=0, exact=False):
+    def __init__(self, gpu, M, K, r, N, dt, scale=1.5, seed=0, exact=False, rounding=False):
         self.M, self.K, self.r, self.N, self.dt, self.scale = M, K, r, N, dt, scale
         if exact:
             x, A, B, base, self.y_want, self.v_want = (t.to(gpu) for t in exact_case(M, K, r, N, dt, seed))
+        elif rounding:
+            x, A, B, base, self.y_want, self.v_want = (t.to(gpu) for t in rounding_case(M, K, r, N, dt, scale, seed))
         else:
             x, A, B, base = (t.to(gpu) for t in drawn_case(M, K, r, N, dt, seed))
         self.x, self.A, self.B, self.base = x, A, B, base
@@ -136,6 +140,52 @@ def test_exact_probes_bit_for_bit(gpu, shape, dt):
             y = _run(case, mode, cfg, gpu)
             want = case.v_want if mode == "null" else case.y_want
             assert torch.equal(y.view(torch.int16), want.view(torch.int16)), (shape, dt, mode, cfg)
+
+
+PROBES = [(1, 32, 8, 16), (5, 96, 24, 80), (33, 384, 128, 192), (128, 384, 64, 192)]
+
+
+def _mismatch(y, want, what):
+    bad = (y.view(torch.int16) != want.view(torch.int16))
+    if bool(bad.any()):
+        m, n = (int(v) for v in bad.nonzero()[0])
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} outputs differ from the header's chain; first at "
+                             f"({m}, {n}): got {float(y[m, n])!r}, the chain gives {float(want[m, n])!r}")
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("scale", [1.5, 0.3])
+@pytest.mark.parametrize("shape", PROBES)
+def test_rounding_probes_bit_for_bit(gpu, shape, scale, dt):
+    """t = rn(x A^T), u = rn(t B^T), v = rn(float(u) * scale), y = rn(float(base) + float(v)): inputs whose
+    fp32 sums are exact in any order (sum |a| |b| below 2^24 in grid units; in fact below 2^18), so the
+    bits are unique, and so large that each rounding changes 5 % of its elements or more.  A kernel that
+    skips a rounding, folds the scale or the base into an unrounded value, or rounds in another mode
+    differs in 6 % of the outputs or more (test_lora_cases_cpu.py)."""
+    case = _case(gpu, *shape, dt, scale=scale, rounding=True)
+    for cfg in CFGS:
+        for mode in MODES:
+            y = _run(case, mode, cfg, gpu)
+            _mismatch(y, case.v_want if mode == "null" else case.y_want, f"{shape} {dt} scale={scale} {mode} cfg={cfg}")
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+def test_rounding_probes_in_one_group(gpu, dt):
+    """Three probes over one x in one call: r = 128 beside 24 and 8, each with its own scale and base mode."""
+    M, K = 33, 384
+    cases = [_case(gpu, M, K, 128, 192, dt, scale=1.5, rounding=True), _case(gpu, M, K, 24, 80, dt, scale=0.3, rounding=True),
+             _case(gpu, M, K, 8, 16, dt, scale=1.5, rounding=True)]
+    x = cases[0].x
+    for c in cases[1:]:
+        assert torch.equal(c.x, x)
+    modes = ("inplace", "null", "separate")
+    for cfg in CFGS:
+        outs = [_guarded(c, m, gpu) for c, m in zip(cases, modes)]
+        rc = _launch(x, M, K, [_desc(c, m, y) for c, m, (_, y) in zip(cases, modes, outs)], dt, cfg)
+        assert rc == _lib.OK
+        for c, m, (buf, y) in zip(cases, modes, outs):
+            assert _bands_intact(buf, c.M * c.N)
+            _mismatch(y, c.v_want if m == "null" else c.y_want, f"grouped N={c.N} r={c.r} {dt} {m} cfg={cfg}")
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])

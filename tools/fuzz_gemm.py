@@ -29,6 +29,11 @@ tests/test_gpu_gemm_family_drawn.py does (its ``Runner``: one workspace per (ent
 every call twice, the suites' own judges).  Round r draws ``--seed`` + r for each of the ten
 (entry, dtype) sequences; ``--cases`` counts calls over all rounds.  One JSON line per failing case
 with its fields.
+
+``--semantics lora``: the fused adapter launch (nf4_lora_add) on the drawn grouped calls of
+tests/_lora_draws.py, run and judged exactly as tests/test_gpu_lora_drawn.py does (its ``Runner``: all
+outputs of a call in one allocation with sentinel gaps, every call twice, the float64 chain's bound).
+Round r draws ``--seed`` + r for both dtypes; ``--cases`` counts calls over all rounds.
 """
 from __future__ import annotations
 
@@ -242,11 +247,42 @@ def family_sweep(args, orc, dev):
                                   "seed": args.seed, "seconds": round(time.time() - t0, 1)}}), flush=True)
 
 
+def lora_sweep(args, dev):
+    """--semantics lora: rounds of the two drawn sequences until --cases or --seconds is reached."""
+    import _lora_draws as D
+    import test_gpu_lora_drawn as T
+
+    t0 = time.time()
+    done = bad = adapters = rounds = 0
+    per_dtype = {dt: 0 for dt in D.DTYPES}
+    while done < args.cases and time.time() - t0 <= args.seconds:
+        seed = args.seed + rounds
+        for dt in D.DTYPES:
+            runner = T.Runner(dt, dev)
+            for c in D.draws(dt, seed):
+                if done >= args.cases or time.time() - t0 > args.seconds:
+                    break
+                try:
+                    runner.run(c)
+                except AssertionError as e:
+                    bad += 1
+                    print(json.dumps({"mismatch": dict(c.fields(), semantics="lora", error=str(e).split("\n", 1)[-1][:400])}), flush=True)
+                done += 1
+                adapters += len(c.adapters)
+                per_dtype[dt] += 1
+        rounds += 1
+        print(json.dumps({"progress": done, "mismatches": bad, "rounds": rounds, "seconds": round(time.time() - t0, 1)}), flush=True)
+    print(json.dumps({"summary": {"semantics": "lora", "cases": done, "launches": 2 * done, "adapters": adapters, "per_dtype": per_dtype,
+                                  "rounds": rounds, "mismatches": bad, "seed": args.seed, "seconds": round(time.time() - t0, 1)}}),
+          flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--semantics", choices=["ref", "bnb", "family"], default="ref",
+    ap.add_argument("--semantics", choices=["ref", "bnb", "family", "lora"], default="ref",
                     help="ref: nf4_gemm_ref and its kin; bnb: nf4_gemm_bnb / nf4_gemm_bnb_single on nf4_quantize's weights; "
-                         "family: the row-tiled and expert GEMMs on the drawn cases of tests/_family_draws.py")
+                         "family: the row-tiled and expert GEMMs on the drawn cases of tests/_family_draws.py; "
+                         "lora: nf4_lora_add on the drawn grouped calls of tests/_lora_draws.py")
     ap.add_argument("--cases", type=int, default=1500)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--seconds", type=float, default=500.0)
@@ -259,6 +295,8 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     L = _lib.lib()
+    if args.semantics == "lora":
+        return lora_sweep(args, dev)
     orc = O.COracle()
     if args.semantics == "family":
         return family_sweep(args, orc, dev)
