@@ -705,6 +705,60 @@ typedef struct {
 int nf4_lora_add(const void* x, int64_t M, int64_t K, const void* mats, int32_t count, int32_t dtype,
                  const void* cfg, void* hip_stream);
 
+/* The adapter tail of a Linear4bit for a batch whose rows belong to DIFFERENT adapters (one NF4
+ * base, many LoRA adapters), one launch for up to NF4DQ_LORA_GROUP_MAX stacks (q/k/v) that share
+ * the activations x [M][K], the ids and the number of adapters S = `adapters`:
+ *   a = adapter_ids[m]        int32 [M] ON THE DEVICE, read when the kernel runs
+ *   0 <= a < S:  y_i[m] = base_i[m] + scale_i[a] * B_i[a] (A_i[a] x[m])
+ *   otherwise (-1, S, INT32_MIN, ..): the row has no adapter; y_i[m] is base_i[m] bit for bit, a
+ *                row of +0 with base NULL, and with base == y nothing is stored.
+ * `stacks` points at `count` nf4_lora_stack descriptors ON THE HOST (read during the call only).
+ * Adapter s of a stack is A + s * a_stride ([r][K]) and B + s * b_stride ([N][r]), strides in
+ * elements; scale is fp32 [S] ON THE DEVICE; an adapter of a smaller rank is zero-padded to the
+ * stack's r by the caller.  A row with an adapter gets nf4_lora_add's rounding chain exactly
+ *   t = rn(sum_k x[m][k] A_a[j][k])   u = rn(sum_j t[j] B_a[n][j])   v = rn(float(u) * scale[a])
+ *   y[m][n] = rn(float(base[m][n]) + float(v))                 base NULL: y = v
+ * with fp32 accumulation, and its summation: the K / 32 chunks split into one contiguous range
+ * per wave, summed in chunk order, the waves' partials in wave order, the expand over r in order.
+ * So a row's bits are a function of x[m], its adapter, base[m], K, r and cfg.waves alone -- not of
+ * M, the row's position or the other rows and ids of the batch -- and equal what nf4_lora_add
+ * stores for that row with that adapter and the same waves; a zero-padded adapter gives the bits
+ * of the unpadded one.  No float atomics, the same bits on every call.  base == y (in place) is
+ * the normal use: every output element is read and written once, by one lane.  Two stacks of one
+ * call must not share output elements.
+ * Domain: nf4_lora_add's (M, K, N, r, count, 16-byte alignment of x, A, B, base, y), and
+ * 1 <= adapters <= NF4DQ_LORA_MAX_ADAPTERS, ids and scale 4-byte aligned, a_stride and b_stride
+ * multiples of 8 with a_stride >= r * K and b_stride >= N * r.
+ * Codes: a null x / adapter_ids / stacks / A / B / scale / y, a dtype that is not fp16 or bf16, a
+ * count, an `adapters` or an r outside its limits, an invalid cfg: NF4DQ_ERR_ARG.  M, K, N or
+ * r % 8 outside the domain, a misaligned pointer, a stride that is no multiple of 8 or smaller
+ * than one adapter: NF4DQ_ERR_SHAPE.  K or N above 2^22, a stride above 2^40:
+ * NF4DQ_ERR_TOO_LARGE.  Checked in that order.
+ * cfg NULL = the library's choice for (M, adapters, the stacks' N, CU count); a nf4_lora_cfg
+ * names tile_n and waves as for nf4_lora_add and never falls back.
+ * The grid is (stack, slot, tile of tile_n columns) with slot < min(adapters, M).  Every wave
+ * reads the M ids and ballots; a workgroup takes the slot-th smallest adapter PRESENT, lists its
+ * rows in LDS in ascending order, forms t for those rows only, expands its tile and scatters the
+ * rows to y; a workgroup whose slot is beyond the adapters present returns before it loads a byte
+ * of x, A or B, and slot 0's workgroups store the rows without an adapter when base != y.  No
+ * workspace, no atomics, no host read of device memory, no workgroup waits for another.
+ * Asynchronous on `hip_stream`; one launch; allocates nothing; capturable in a graph, and a
+ * replay follows whatever ids the buffer then holds. */
+#define NF4DQ_LORA_MAX_ADAPTERS 64
+typedef struct {
+    const void* A;      /* [S][r][K], adapter s at A + s * a_stride elements */
+    const void* B;      /* [S][N][r], adapter s at B + s * b_stride elements */
+    const float* scale; /* [S] fp32, ON THE DEVICE */
+    const void* base;   /* [M][N], or NULL; may be y */
+    void* y;            /* [M][N] */
+    int64_t N;
+    int64_t a_stride;
+    int64_t b_stride;
+    int32_t r;          /* the stack's rank; a smaller adapter is zero-padded by the caller */
+} nf4_lora_stack;
+int nf4_lora_add_routed(const void* x, const void* adapter_ids, int64_t M, int64_t K, int32_t adapters,
+                        const void* stacks, int32_t count, int32_t dtype, const void* cfg, void* hip_stream);
+
 /* The split-K hand-off never hangs: a reducer that has polled a partner slice's
  * entries 2^16 times without seeing them gives up, reads them as NaN and sets a
  * sticky error word in the workspace header.  This call waits for `hip_stream`,

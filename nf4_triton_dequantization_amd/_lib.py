@@ -131,6 +131,17 @@ class LoraMat(ctypes.Structure):
                 ("N", ctypes.c_int64), ("r", ctypes.c_int32), ("scale", ctypes.c_float)]
 
 
+LORA_MAX_ADAPTERS = 64  # NF4DQ_LORA_MAX_ADAPTERS: adapters of one stack of nf4_lora_add_routed
+
+
+class LoraStack(ctypes.Structure):
+    """nf4_lora_stack (include/nf4_dequant.h): one stack of adapters of nf4_lora_add_routed."""
+
+    _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("base", ctypes.c_void_p),
+                ("y", ctypes.c_void_p), ("N", ctypes.c_int64), ("a_stride", ctypes.c_int64), ("b_stride", ctypes.c_int64),
+                ("r", ctypes.c_int32)]
+
+
 class LoraCfg(ctypes.Structure):
     """nf4_lora_cfg (include/nf4_dequant.h)."""
 
@@ -209,6 +220,8 @@ SIGNATURES = {
                                              ctypes.POINTER(GemmCfg), _P]),
     # `mats`: const void* in the header, pointing at LoraMat[count]; `cfg`: NULL or one LoraCfg
     "nf4_lora_add": (ctypes.c_int, [_P, _I64, _I64, _P, _I32, _I32, _P, _P]),
+    # `adapter_ids`: int32 on the device; `stacks`: const void* in the header, pointing at LoraStack[count]
+    "nf4_lora_add_routed": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _I32, _I32, _P, _P]),
     "nf4_gemm_check_workspace": (ctypes.c_int, [_P, ctypes.c_size_t, _P]),
     "nf4_strerror": (ctypes.c_char_p, [ctypes.c_int]),
     "nf4_version": (ctypes.c_char_p, []),

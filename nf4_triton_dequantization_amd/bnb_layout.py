@@ -289,6 +289,86 @@ class LoraLinear4bit(nn.Module):
                                    self.base_layer.bias)
 
 
+class MultiLoraLinear4bit(nn.Module):
+    """One ``Linear4bit`` serving MANY low-rank adapters at once: row m of a batch takes adapter
+    ``adapter_ids[m]``, a row whose id is outside ``0..S-1`` (-1, say) the base alone.  Inference
+    form, no dropout, as ``LoraLinear4bit``.
+
+    ``base_layer`` is the wrapped ``Linear4bit``; ``lora_A`` (``[S, r, in_features]``) and ``lora_B``
+    (``[S, out_features, r]``) are parameters holding the S adapters stacked, each zero-padded to
+    the stack's rank r; ``scaling`` is an fp32 buffer ``[S]`` and ``ranks`` the adapters' own ranks.
+    ``forward(x, adapter_ids)`` is ``kernel.nf4_linear_multilora_bnb``: one routed launch for the
+    whole tail where that is routed -- capturable in a graph, the ids read at replay -- and the
+    composite, which autograd follows to ``lora_A`` and ``lora_B``, everywhere else.
+    """
+
+    def __init__(self, base_layer: Linear4bit, lora_A: torch.Tensor, lora_B: torch.Tensor, scaling: torch.Tensor,
+                 ranks=None):
+        super().__init__()
+        if lora_A.dim() != 3 or lora_B.dim() != 3 or lora_A.shape[0] != lora_B.shape[0] \
+                or tuple(lora_A.shape[1:]) != (lora_B.shape[2], base_layer.in_features) \
+                or lora_B.shape[1] != base_layer.out_features:
+            raise ValueError(f"MultiLoraLinear4bit: lora_A must be [S, r, {base_layer.in_features}] and lora_B "
+                             f"[S, {base_layer.out_features}, r], got {tuple(lora_A.shape)} and {tuple(lora_B.shape)}")
+        self.base_layer = base_layer
+        self.lora_A = nn.Parameter(lora_A, requires_grad=lora_A.requires_grad)
+        self.lora_B = nn.Parameter(lora_B, requires_grad=lora_B.requires_grad)
+        scaling = torch.as_tensor(scaling, dtype=torch.float32, device=lora_A.device).reshape(-1)
+        if scaling.numel() != lora_A.shape[0]:
+            raise ValueError(f"MultiLoraLinear4bit: {scaling.numel()} scalings for {lora_A.shape[0]} adapters")
+        self.register_buffer("scaling", scaling.contiguous())
+        self.in_features, self.out_features = base_layer.in_features, base_layer.out_features
+        self.num_adapters, self.r = int(lora_A.shape[0]), int(lora_A.shape[1])
+        self.ranks = [self.r] * self.num_adapters if ranks is None else [int(v) for v in ranks]
+
+    @classmethod
+    def from_linear4bit(cls, base: Linear4bit, adapters, dtype=None):
+        """Stack ``adapters``, a list of ``(lora_A [r_i, K], lora_B [N, r_i], scaling_i)``, on ``base``:
+        each is zero-padded to the largest ``r_i`` rounded up to a multiple of 8 (exact zeros add
+        nothing to a sum, so an adapter's results do not depend on the padding).  ``dtype``
+        defaults to ``quant_state.dtype`` (the fused route needs the two equal); the stacks live on
+        the weight's device and record no gradient."""
+        adapters = list(adapters)
+        if not adapters:
+            raise ValueError("MultiLoraLinear4bit.from_linear4bit: at least one adapter")
+        N, K = int(base.out_features), int(base.in_features)
+        for i, (A, B, _) in enumerate(adapters):
+            if A.dim() != 2 or B.dim() != 2 or A.shape[0] < 1 or tuple(A.shape) != (A.shape[0], K) \
+                    or tuple(B.shape) != (N, A.shape[0]):
+                raise ValueError(f"MultiLoraLinear4bit.from_linear4bit: adapter {i} must be ([r, {K}], [{N}, r], scaling), "
+                                 f"got {tuple(A.shape)} and {tuple(B.shape)}")
+        dev = base.weight.data.device
+        dtype = dtype if dtype is not None else base.weight.quant_state.dtype
+        ranks = [int(A.shape[0]) for A, _, _ in adapters]
+        r = -(-max(ranks) // 8) * 8
+        lora_A = torch.zeros(len(adapters), r, K, dtype=dtype, device=dev)
+        lora_B = torch.zeros(len(adapters), N, r, dtype=dtype, device=dev)
+        for s, (A, B, _) in enumerate(adapters):
+            lora_A[s, :ranks[s]] = A.detach().to(device=dev, dtype=dtype)
+            lora_B[s, :, :ranks[s]] = B.detach().to(device=dev, dtype=dtype)
+        scaling = torch.tensor([float(sc) for _, _, sc in adapters], dtype=torch.float32, device=dev)
+        return cls(base, lora_A, lora_B, scaling, ranks)
+
+    def adapter(self, s: int) -> "LoraLinear4bit":
+        """Adapter ``s`` alone as a ``LoraLinear4bit`` over the same base: its ``lora_A`` / ``lora_B``
+        weights are VIEWS of this module's stacks (the adapter's own rank, without the padding)."""
+        if not 0 <= s < self.num_adapters:
+            raise IndexError(f"MultiLoraLinear4bit.adapter: {s} is outside 0..{self.num_adapters - 1}")
+        r = self.ranks[s]
+        A, B = self.lora_A.detach()[s, :r], self.lora_B.detach()[s, :, :r]
+        la = nn.Linear(self.in_features, r, bias=False, device="meta")
+        lb = nn.Linear(r, self.out_features, bias=False, device="meta")
+        la.weight = nn.Parameter(A, requires_grad=False)
+        lb.weight = nn.Parameter(B, requires_grad=False)
+        return LoraLinear4bit(self.base_layer, la, lb, float(self.scaling[s]))
+
+    def forward(self, x: torch.Tensor, adapter_ids: torch.Tensor) -> torch.Tensor:
+        from .kernel import nf4_linear_multilora_bnb
+
+        return nf4_linear_multilora_bnb(x, self.base_layer, self.lora_A, self.lora_B, self.scaling, adapter_ids,
+                                        self.base_layer.bias)
+
+
 class Embedding4bit(nn.Module):
     """``bitsandbytes.nn.Embedding4bit`` / ``EmbeddingNF4`` stand-in: a token embedding whose
     ``[num_embeddings, embedding_dim]`` table is NF4 storage (a ``Params4bit``).

@@ -1508,3 +1508,204 @@ def nf4_linear_lora_bnb_grouped(x: torch.Tensor, modules: Sequence, adapters: Se
         _lora_add(x, M, K, dtype, items)
     return [y if f or ad is None else _lora_composite(y, x, ad[0], ad[1], ad[2])
             for y, ad, f in zip(ys, adapters, fused)]
+
+
+# Rows at which nf4_linear_multilora_bnb and nf4_linear_multilora_bnb_grouped take the routed
+# adapter launch (nf4_lora_add_routed).  Set from tools/bench_multilora.py's measurement and from
+# nothing else, by LORA_ROUTED_*'s rule: a row count is routed only where, at every shape, rank
+# and routing measured, the slower of the launch's two runs beats the faster of the composite's
+# two runs by more than the spread of a route's rounds (profiles/multilora/, README, DESIGN
+# section 4b "The multi-adapter tail").  Measured at 4096^2, 14336x4096 and 4096x14336 with r = 16
+# and 64 under three routings (every row its own adapter, 4 adapters uniform, one adapter of 64):
+# the launch wins all 18 tail cells and all 18 base-plus-tail cells at each of 1, 8, 32, 64 and 128
+# rows (by 1.10x at the least: one row, r = 64, K = 14336), so every row count the entry takes is routed.
+MULTILORA_ROUTED_MIN_M = 1
+MULTILORA_ROUTED_MAX_M = 128
+MULTILORA_CHUNK_ROWS = 32  # rows per gather of the composite: bounds its [rows, r, K] temporary
+
+
+def _multilora_scaling(scaling, S: int, device) -> torch.Tensor:
+    """``scaling`` as an fp32 tensor [S] on ``device`` (a sequence of floats is copied there)."""
+    if not isinstance(scaling, torch.Tensor):
+        scaling = torch.tensor([float(s) for s in scaling], dtype=torch.float32, device=device)
+    if scaling.dim() != 1 or scaling.numel() != S:
+        raise ValueError(f"nf4_linear_multilora_bnb: scaling must hold one value per adapter ({S}), got "
+                         f"{tuple(scaling.shape)}")
+    return scaling
+
+
+def _multilora_check(x: torch.Tensor, module, A: torch.Tensor, B: torch.Tensor, ids: torch.Tensor) -> int:
+    """The argument rules of nf4_linear_multilora_bnb; returns the row count M."""
+    N, K = int(module.out_features), int(module.in_features)
+    if A.dim() != 3 or B.dim() != 3 or A.shape[0] != B.shape[0] or A.shape[0] < 1:
+        raise ValueError(f"nf4_linear_multilora_bnb: lora_A must be [S, r, K] and lora_B [S, N, r], got "
+                         f"{tuple(A.shape)} and {tuple(B.shape)}")
+    S, r = int(A.shape[0]), int(A.shape[1])
+    if tuple(A.shape) != (S, r, K) or tuple(B.shape) != (S, N, r):
+        raise ValueError(f"nf4_linear_multilora_bnb: lora_A {tuple(A.shape)} / lora_B {tuple(B.shape)} do not fit a "
+                         f"[{N}, {K}] weight with {S} adapters of rank {r}")
+    if x.shape[-1] != K:
+        raise ValueError(f"nf4_linear_multilora_bnb: x has {x.shape[-1]} features, the weight takes {K}")
+    M = x.numel() // K
+    if ids.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"nf4_linear_multilora_bnb: adapter_ids must be int32 or int64, got {ids.dtype}")
+    if ids.numel() != M:
+        raise ValueError(f"nf4_linear_multilora_bnb: {ids.numel()} adapter ids for {M} rows of x")
+    return M
+
+
+def _multilora_composite(y: torch.Tensor, x: torch.Tensor, A: torch.Tensor, B: torch.Tensor, scaling: torch.Tensor,
+                         ids: torch.Tensor) -> torch.Tensor:
+    """The definition of the multi-adapter tail: what autograd follows.  No host read."""
+    S, K, N = int(A.shape[0]), int(A.shape[2]), int(B.shape[1])
+    x2 = x.reshape(-1, K).to(A.dtype)
+    y2 = y.reshape(-1, N)
+    ids = ids.reshape(-1)
+    scaling = scaling.to(device=ids.device, dtype=torch.float32)
+    valid = (ids >= 0) & (ids < S)
+    idc = ids.clamp(0, S - 1).long()
+    outs = []
+    for i in range(0, x2.shape[0], MULTILORA_CHUNK_ROWS):
+        sl = slice(i, i + MULTILORA_CHUNK_ROWS)
+        t = torch.bmm(A[idc[sl]], x2[sl].unsqueeze(-1))
+        u = torch.bmm(B[idc[sl]], t).squeeze(-1)
+        v = (u * scaling[idc[sl]].unsqueeze(-1)).to(y.dtype)  # fp32 product, one rounding
+        outs.append(torch.where(valid[sl].unsqueeze(-1), y2[sl] + v, y2[sl]))
+    if not outs:
+        return y
+    return (outs[0] if len(outs) == 1 else torch.cat(outs)).reshape(y.shape)
+
+
+def _multilora_fusable(x: torch.Tensor, module, A: torch.Tensor, B: torch.Tensor, scaling: torch.Tensor,
+                       ids: torch.Tensor, M: int) -> bool:
+    """nf4_linear_multilora_bnb's fused-path rules (its docstring) for one stack: _lora_fusable's,
+    on [S, r, K] / [S, N, r]."""
+    dtype = module.weight.quant_state.dtype
+    dev = module.weight.data.device
+    N, K = int(module.out_features), int(module.in_features)
+    S, r = int(A.shape[0]), int(A.shape[1])
+    return (dev.type == "cuda" and x.device == dev and A.device == dev and B.device == dev and ids.device == dev
+            and scaling.device == dev and scaling.dtype == torch.float32 and scaling.is_contiguous()
+            and dtype in (torch.float16, torch.bfloat16) and A.dtype == dtype and B.dtype == dtype
+            and max(1, MULTILORA_ROUTED_MIN_M) <= M <= min(MULTILORA_ROUTED_MAX_M, _lib.LORA_MAX_M)
+            and 1 <= S <= _lib.LORA_MAX_ADAPTERS and r % 8 == 0 and 8 <= r <= _lib.LORA_MAX_R
+            and K % 32 == 0 and K >= 32 and N % 16 == 0 and N >= 16
+            and A.is_contiguous() and B.is_contiguous() and A.data_ptr() % 16 == 0 and B.data_ptr() % 16 == 0
+            and scaling.data_ptr() % 4 == 0
+            and not (torch.is_grad_enabled() and (x.requires_grad or A.requires_grad or B.requires_grad
+                                                  or scaling.requires_grad)))
+
+
+def _multilora_ids32(ids: torch.Tensor, S: int) -> torch.Tensor:
+    """The ids as the entry takes them: int32, contiguous.  int64 ids are clamped to [-1, S] first,
+    so that a value beyond 32 bits stays "no adapter" instead of wrapping into range."""
+    ids = ids.reshape(-1)
+    if ids.dtype != torch.int32:
+        ids = ids.clamp(-1, S).to(torch.int32)
+    return ids.contiguous()
+
+
+def _multilora_add(x: torch.Tensor, M: int, K: int, dtype: torch.dtype, ids32: torch.Tensor, S: int, items) -> None:
+    """ONE nf4_lora_add_routed launch: ``items`` is [(y [.., N] contiguous, updated in place, A [S, r, K],
+    B [S, N, r], scaling fp32 [S])]."""
+    dev = x.device
+    xc = x.reshape(M, K)
+    if xc.dtype != dtype:
+        xc = xc.to(dtype)
+    xc = xc.contiguous()
+    if xc.data_ptr() % 16:
+        xc = xc.clone()  # a view at an odd offset: the entry loads 16 bytes at a time
+    stacks = (_lib.LoraStack * len(items))()
+    for i, (y, A, B, scaling) in enumerate(items):
+        r, N = int(A.shape[1]), int(B.shape[1])
+        stacks[i] = _lib.LoraStack(A.data_ptr(), B.data_ptr(), scaling.data_ptr(), y.data_ptr(), y.data_ptr(), N,
+                                   r * K, N * r, r)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().nf4_lora_add_routed(xc.data_ptr(), ids32.data_ptr(), M, K, S,
+                                            ctypes.cast(stacks, ctypes.c_void_p), len(items), _dtype_code(dtype), None,
+                                            torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "nf4 routed lora add")
+
+
+def nf4_linear_multilora_bnb(x: torch.Tensor, module, lora_A: torch.Tensor, lora_B: torch.Tensor, scaling,
+                             adapter_ids: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A ``Linear4bit`` in bitsandbytes semantics whose batch rows belong to DIFFERENT low-rank
+    adapters (one NF4 base, many LoRA adapters): row m gets ``W x + b + scaling[a] * B[a] (A[a] x)``
+    with ``a = adapter_ids[m]``.  ``lora_A`` is ``[S, r, K]`` and ``lora_B`` ``[S, N, r]`` (an adapter
+    of a smaller rank zero-padded to r), ``scaling`` an fp32 tensor ``[S]`` or a sequence of S
+    floats, ``adapter_ids`` int32 or int64 with one id per row of x (x's leading dims flattened);
+    an id outside ``0..S-1`` (-1, say) means the row has no adapter and gets the base alone, bit
+    for bit.  Its definition, which is also its fallback and what autograd follows::
+
+        y = nf4_linear_bnb(x, module, bias)
+        valid = (ids >= 0) & (ids < S)
+        idc = ids.clamp(0, S - 1)
+        t = torch.bmm(lora_A[idc], x2.to(lora_A.dtype).unsqueeze(-1))
+        u = torch.bmm(lora_B[idc], t).squeeze(-1)
+        v = (u * scaling[idc].unsqueeze(-1)).to(y.dtype)     # fp32 product, one rounding
+        torch.where(valid.unsqueeze(-1), y + v, y)
+
+    in chunks of ``MULTILORA_CHUNK_ROWS`` rows, which bound the gathered ``[rows, r, K]`` tensor.  It
+    reads nothing on the host, so it is itself capturable in a graph.
+
+    The fused route runs the base through ``nf4_linear_bnb`` and the whole tail as ONE launch
+    (``nf4_lora_add_routed``) that finds the adapters present on the device and updates the base's
+    result in place, with ``nf4_lora_add``'s rounding chain per row; a captured graph follows
+    whatever ids the buffer holds at replay.  It is taken under ``nf4_linear_lora_bnb``'s rules --
+    tensors on the GPU, the adapters' dtype equal to ``quant_state.dtype`` (fp16 or bf16),
+    ``K % 32 == 0``, ``N % 16 == 0``, ``r % 8 == 0`` with ``8 <= r <= 128``, contiguous and 16-byte
+    aligned stacks, no gradient being recorded -- with ``S <= 64``, ``scaling`` an fp32 tensor on the
+    device (a sequence is copied there first) and ``MULTILORA_ROUTED_MIN_M <= M <=
+    MULTILORA_ROUTED_MAX_M`` rows.  int64 ids cost one clamp and one cast.  Everything else takes
+    the composite.  The summation order of the two products may differ between the routes, so the
+    last bits may.
+    """
+    M = _multilora_check(x, module, lora_A, lora_B, adapter_ids)
+    S, K = int(lora_A.shape[0]), int(module.in_features)
+    scaling = _multilora_scaling(scaling, S, lora_A.device)
+    y = nf4_linear_bnb(x, module, bias)
+    dtype = module.weight.quant_state.dtype
+    if not (_multilora_fusable(x, module, lora_A, lora_B, scaling, adapter_ids, M) and _lora_base_in_place(y, dtype)):
+        return _multilora_composite(y, x, lora_A, lora_B, scaling, adapter_ids)
+    _multilora_add(x, M, K, dtype, _multilora_ids32(adapter_ids, S), S, [(y, lora_A, lora_B, scaling)])
+    return y
+
+
+def nf4_linear_multilora_bnb_grouped(x: torch.Tensor, modules: Sequence, stacks: Sequence, adapter_ids: torch.Tensor,
+                                     biases: Optional[Sequence] = None) -> List[torch.Tensor]:
+    """``nf4_linear_multilora_bnb`` for ``Linear4bit`` weights that share the input x and the ids
+    (q/k/v, gate/up): ``stacks[i]`` is ``(lora_A [S, r_i, K], lora_B [S, N_i, r_i], scaling)`` or
+    ``None`` for a module without adapters.  The base goes through ``nf4_linear_bnb_grouped``; ALL
+    stacks that meet the fused-path rules and hold the same number of adapters go in ONE
+    ``nf4_lora_add_routed`` launch when there are at most ``LORA_GROUP_MAX`` of them (each updates
+    its module's result in place), every other stack takes the composite.
+    """
+    modules = list(modules)
+    stacks = list(stacks)
+    if len(stacks) != len(modules):
+        raise ValueError("nf4_linear_multilora_bnb_grouped: one stack (or None) per module")
+    checked = []
+    for mod, st in zip(modules, stacks):
+        if st is None:
+            checked.append(None)
+            continue
+        _multilora_check(x, mod, st[0], st[1], adapter_ids)
+        checked.append((st[0], st[1], _multilora_scaling(st[2], int(st[0].shape[0]), st[0].device)))
+    ys = nf4_linear_bnb_grouped(x, modules, biases)
+    if not modules:
+        return ys
+    K = int(modules[0].in_features)
+    M = x.numel() // K if K and x.shape[-1] == K else 0
+    dtype = modules[0].weight.quant_state.dtype
+    S = next((int(st[0].shape[0]) for st in checked if st is not None), 0)
+    fused = [st is not None and int(mod.in_features) == K and mod.weight.quant_state.dtype == dtype
+             and int(st[0].shape[0]) == S and _multilora_fusable(x, mod, st[0], st[1], st[2], adapter_ids, M)
+             and _lora_base_in_place(y, dtype)
+             for mod, st, y in zip(modules, checked, ys)]
+    if not 1 <= sum(fused) <= _lib.LORA_GROUP_MAX:
+        fused = [False] * len(modules)
+    items = [(y, st[0], st[1], st[2]) for y, st, f in zip(ys, checked, fused) if f]
+    if items:
+        _multilora_add(x, M, K, dtype, _multilora_ids32(adapter_ids, S), S, items)
+    return [y if f or st is None else _multilora_composite(y, x, st[0], st[1], st[2], adapter_ids)
+            for y, st, f in zip(ys, checked, fused)]
