@@ -723,7 +723,10 @@ int nf4_lora_add(const void* x, int64_t M, int64_t K, const void* mats, int32_t 
  * So a row's bits are a function of x[m], its adapter, base[m], K, r and cfg.waves alone -- not of
  * M, the row's position or the other rows and ids of the batch -- and equal what nf4_lora_add
  * stores for that row with that adapter and the same waves; a zero-padded adapter gives the bits
- * of the unpadded one.  No float atomics, the same bits on every call.  base == y (in place) is
+ * of the unpadded one for every row of x that is finite.  A row of x that holds an infinity meets
+ * the padding as inf * 0 = NaN in the padded columns of t, so its whole output row is NaN where the
+ * unpadded adapter gives infinities: the chain above on the padded matrices, not a special case.
+ * No float atomics, the same bits on every call.  base == y (in place) is
  * the normal use: every output element is read and written once, by one lane.  Two stacks of one
  * call must not share output elements.
  * Domain: nf4_lora_add's (M, K, N, r, count, 16-byte alignment of x, A, B, base, y), and

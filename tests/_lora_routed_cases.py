@@ -2,7 +2,15 @@
 test_gpu_multilora_api.py: one case of _lora_cases.py per adapter present (drawn, exact probe or
 rounding probe, seeded by the adapter), the rows interleaved as the id vector says, so every
 adapter group keeps its own oracle, bound and expected bits.  Rows whose id is outside 0..S-1 are
-drawn rows with a base of their own; adapters no row names are drawn too."""
+drawn rows with a base of their own; adapters no row names are drawn too.
+
+``a_pad`` / ``b_pad`` (elements, multiples of 8) put adapter s at A + s * (r * K + a_pad) and
+B + s * (N * r + b_pad), the padding filled with the 16-bit NaN pattern 0x7FFF: ``a_stride`` and
+``b_stride`` are what the descriptor must name, and ``A`` / ``B`` are strided views of the padded
+buffers.  ``poison_absent`` makes everything the launch must not use a NaN: the A, B and scale of
+every adapter no valid id names, and the x rows of the rows without an adapter.  No expected output
+changes: those rows are the base bit for bit and an absent adapter contributes nothing.  ``scales``
+replaces ``scale_of`` (one per adapter)."""
 from __future__ import annotations
 
 import numpy as np
@@ -44,10 +52,24 @@ def scale_of(a):
     return f32((0.3 + 0.37 * (a % 7)) * (-1.0) ** a)
 
 
+PAD_BITS = 0x7FFF                                   # a NaN in both 16-bit formats
+
+
+def _padded(t, pad, dev):
+    """[S, a, b] on the device as a view of a buffer [S, a * b + pad] whose padding is PAD_BITS."""
+    S, a, b = t.shape
+    buf = torch.full((S, a * b + pad), PAD_BITS, dtype=torch.int16)
+    buf[:, :a * b] = t.reshape(S, a * b).view(torch.int16)
+    view = buf.to(dev).view(t.dtype)[:, :a * b].unflatten(1, (a, b))
+    assert view.stride()[1:] == (b, 1) and (S == 1 or view.stride(0) == a * b + pad)
+    return view
+
+
 class Routed:
     """One routed call's inputs on the device with the references of every adapter group."""
 
-    def __init__(self, dev, K, r, N, dt, S, ids, kind="drawn", own_r=None, seed=0):
+    def __init__(self, dev, K, r, N, dt, S, ids, kind="drawn", own_r=None, seed=0, a_pad=0, b_pad=0, poison_absent=False,
+                 scales=None):
         self.M, self.K, self.r, self.N, self.dt, self.S, self.kind = len(ids), K, r, N, dt, S, kind
         self.id_list = list(ids)
         own_r = r if own_r is None else own_r           # the adapters' own rank, zero-padded to the stack's r
@@ -62,7 +84,9 @@ class Routed:
             if 0 <= a < S:
                 self.groups.setdefault(a, []).append(m)
         self.none = [m for m, a in enumerate(ids) if not 0 <= a < S]
-        self.scales = [0.5 if kind == "exact" else scale_of(a) for a in range(S)]
+        self.scales = [0.5 if kind == "exact" else scale_of(a) for a in range(S)] if scales is None else [f32(v) for v in scales]
+        assert len(self.scales) == S and a_pad >= 0 and b_pad >= 0 and a_pad % 8 == 0 and b_pad % 8 == 0
+        self.a_stride, self.b_stride = r * K + a_pad, N * r + b_pad
         self.want = {}                                   # adapter -> (y_want, v_want) of the probes
         for a in range(S):
             rows = self.groups.get(a)
@@ -82,8 +106,17 @@ class Routed:
             xa, _, _, ba = drawn_case(len(self.none), K, own_r, N, dt, seed + 99)
             x[self.none], base[self.none] = xa, ba
             base[self.none[0], ::2] = -0.0               # a -0 base stays -0
-        self.x, self.base, self.A, self.B = x.to(dev), base.to(dev), A.to(dev), B.to(dev)
-        self.scale = torch.tensor(self.scales, dtype=torch.float32, device=dev)
+        dev_scales = list(self.scales)
+        if poison_absent:                                # NaN values in mapped memory: whatever reads them shows
+            for a in range(S):
+                if a not in self.groups:
+                    A[a], B[a], dev_scales[a] = float("nan"), float("nan"), float("nan")
+            if self.none:
+                x[self.none] = float("nan")
+        self.x, self.base = x.to(dev), base.to(dev)
+        self.A = A.to(dev) if not a_pad else _padded(A, a_pad, dev)
+        self.B = B.to(dev) if not b_pad else _padded(B, b_pad, dev)
+        self.scale = torch.tensor(dev_scales, dtype=torch.float32, device=dev)
         self.ids = torch.tensor(self.id_list, dtype=torch.int32, device=dev)
         self.ref = {}
         for a, rows in self.groups.items():

@@ -68,7 +68,7 @@ def _bands_intact(buf, n):
 def _stack(c, mode, y, base=None):
     base = c.base if base is None else base
     bp = {"null": None, "inplace": y.data_ptr(), "separate": base.data_ptr()}[mode]
-    return _lib.LoraStack(c.A.data_ptr(), c.B.data_ptr(), c.scale.data_ptr(), bp, y.data_ptr(), c.N, c.r * c.K, c.N * c.r, c.r)
+    return _lib.LoraStack(c.A.data_ptr(), c.B.data_ptr(), c.scale.data_ptr(), bp, y.data_ptr(), c.N, c.a_stride, c.b_stride, c.r)
 
 
 def _launch(x, ids, M, K, S, stacks, dt, cfg):

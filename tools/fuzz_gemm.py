@@ -34,6 +34,11 @@ with its fields.
 tests/_lora_draws.py, run and judged exactly as tests/test_gpu_lora_drawn.py does (its ``Runner``: all
 outputs of a call in one allocation with sentinel gaps, every call twice, the float64 chain's bound).
 Round r draws ``--seed`` + r for both dtypes; ``--cases`` counts calls over all rounds.
+
+``--semantics lora_routed``: the routed adapter launch (nf4_lora_add_routed) on the drawn calls of
+tests/_lora_routed_draws.py, run and judged exactly as tests/test_gpu_lora_routed_drawn.py does (its
+``Runner``: padded strides, NaN in everything absent, every call twice, the float64 chain's bound per
+adapter group, nf4_lora_add's bits under an explicit cfg).  Rounds and ``--cases`` as for ``lora``.
 """
 from __future__ import annotations
 
@@ -248,12 +253,17 @@ def family_sweep(args, orc, dev):
 
 
 def lora_sweep(args, dev):
-    """--semantics lora: rounds of the two drawn sequences until --cases or --seconds is reached."""
-    import _lora_draws as D
-    import test_gpu_lora_drawn as T
+    """--semantics lora / lora_routed: rounds of the two drawn sequences until --cases or --seconds is reached."""
+    routed = args.semantics == "lora_routed"
+    if routed:
+        import _lora_routed_draws as D
+        import test_gpu_lora_routed_drawn as T
+    else:
+        import _lora_draws as D
+        import test_gpu_lora_drawn as T
 
     t0 = time.time()
-    done = bad = adapters = rounds = 0
+    done = bad = adapters = rounds = launches = 0
     per_dtype = {dt: 0 for dt in D.DTYPES}
     while done < args.cases and time.time() - t0 <= args.seconds:
         seed = args.seed + rounds
@@ -266,23 +276,25 @@ def lora_sweep(args, dev):
                     runner.run(c)
                 except AssertionError as e:
                     bad += 1
-                    print(json.dumps({"mismatch": dict(c.fields(), semantics="lora", error=str(e).split("\n", 1)[-1][:400])}), flush=True)
+                    print(json.dumps({"mismatch": dict(c.fields(), semantics=args.semantics, error=str(e).split("\n", 1)[-1][:400])}), flush=True)
                 done += 1
-                adapters += len(c.adapters)
+                adapters += len(c.stacks) * len(c.groups) if routed else len(c.adapters)  # routed: adapter groups judged
                 per_dtype[dt] += 1
+            launches += runner.launches
         rounds += 1
         print(json.dumps({"progress": done, "mismatches": bad, "rounds": rounds, "seconds": round(time.time() - t0, 1)}), flush=True)
-    print(json.dumps({"summary": {"semantics": "lora", "cases": done, "launches": 2 * done, "adapters": adapters, "per_dtype": per_dtype,
+    print(json.dumps({"summary": {"semantics": args.semantics, "cases": done, "launches": launches, "adapters": adapters, "per_dtype": per_dtype,
                                   "rounds": rounds, "mismatches": bad, "seed": args.seed, "seconds": round(time.time() - t0, 1)}}),
           flush=True)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--semantics", choices=["ref", "bnb", "family", "lora"], default="ref",
+    ap.add_argument("--semantics", choices=["ref", "bnb", "family", "lora", "lora_routed"], default="ref",
                     help="ref: nf4_gemm_ref and its kin; bnb: nf4_gemm_bnb / nf4_gemm_bnb_single on nf4_quantize's weights; "
                          "family: the row-tiled and expert GEMMs on the drawn cases of tests/_family_draws.py; "
-                         "lora: nf4_lora_add on the drawn grouped calls of tests/_lora_draws.py")
+                         "lora: nf4_lora_add on the drawn grouped calls of tests/_lora_draws.py; "
+                         "lora_routed: nf4_lora_add_routed on the drawn calls of tests/_lora_routed_draws.py")
     ap.add_argument("--cases", type=int, default=1500)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--seconds", type=float, default=500.0)
@@ -295,7 +307,7 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     L = _lib.lib()
-    if args.semantics == "lora":
+    if args.semantics in ("lora", "lora_routed"):
         return lora_sweep(args, dev)
     orc = O.COracle()
     if args.semantics == "family":
