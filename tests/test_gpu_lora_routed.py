@@ -14,7 +14,8 @@ routing under every base mode at the mask and tile edges is a test of its own.  
 output lies between sentinel bands that must stay untouched and starts as NaN wherever the launch
 must write it.  Further: three stacks in one call, every cfg, the exact and the rounding-chain
 probes, batch invariance (rows permuted, rows dropped), bit equality with nf4_lora_add per adapter
-at the same waves (also for adapters zero-padded from r = 24 to a stack rank of 40), the same bits
+at the same waves (also for adapters zero-padded from r = 24 to a stack rank of 40; and once per
+instantiation of the kernel template, all 16), the same bits
 on every call, and the rows without an adapter."""
 import ctypes
 import itertools
@@ -221,6 +222,20 @@ def test_rows_have_the_bits_of_nf4_lora_add_at_the_same_waves(gpu, dt):
                     if own_r is not None:                # the unpadded adapter: exact zeros add nothing
                         ya = _lora_add(c, a, rows, mode, (64, waves), gpu, own=True)
                         assert torch.equal(_bits(y[rows]), _bits(ya)), (M, name, waves, mode, a, "unpadded")
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+def test_every_instantiation_matches_nf4_lora_add(gpu, dt):
+    """r in {8, 24, 40, 128} are the 1, 2, 4 and 8 r tiles, M in {5, 17} the one and two row tiles per
+    row block: with the dtype, all 16 instantiations of either kernel.  Every row on adapter 2 of 3,
+    so the routed launch's one live slot does nf4_lora_add's whole work: the same bits."""
+    for r, M in itertools.product(RS, (5, 17)):
+        S, ids = routing("one", M, 3)
+        assert S == 3 and ids == [2] * M
+        c = _case(gpu, 96, r, 80, dt, S, ids)
+        y = _run(c, "separate", (64, 2), gpu)
+        ya = _lora_add(c, 2, list(range(M)), "separate", (64, 2), gpu, own=False)
+        assert torch.equal(_bits(y), _bits(ya)), (r, M)
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])

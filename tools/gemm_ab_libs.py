@@ -22,6 +22,15 @@ five) any bit that differs from build A's ends the run:
 their sums run in MFMA order over the chunks and in slice order in the reducer in every build,
 so anything but equality is a behaviour change.  For the older entries, whose builds may
 legitimately order a sum differently, the line only reports ``bit_equal``.
+
+The adapter launches ``nf4_lora_add`` and ``nf4_lora_add_routed`` are exact entries too (chunk
+order in a wave, wave order in the sum).  Their points: ``--lora-shapes`` (N,K) x ``--ranks`` x
+``--lora-ms``, bf16, in place on a resident base, the library's cfg, 8 rotating adapters or stacks;
+the routed entry under the routings ``own`` (S = min(M, 64), every row its own adapter while they
+last) and ``one`` (one adapter of a stack of 64), as tools/bench_multilora.py builds them.  Every
+build starts from the same base and its 8 launches accumulate in place before the comparison.
+The timed replays then go on accumulating into the same outputs: those values mean nothing and
+may overflow, which is harmless here because these kernels' time does not depend on the data.
 """
 from __future__ import annotations
 
@@ -37,13 +46,14 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 from nf4_triton_dequantization_amd import _lib  # noqa: E402
 from tools.bench_gemm import _interleaved_rounds  # noqa: E402
+from tools.bench_multilora import make_routing  # noqa: E402
 
 ENTRIES = ("nf4_gemm_ref", "nf4_gemm_ref_grouped", "nf4_gemm_bnb", "nf4_gemm_workspace_bytes",
            "nf4_gemm_grouped_workspace_bytes", "nf4_gemm_bnb_workspace_bytes", "nf4_gemm_check_workspace",
            "nf4_gemm_bnb_mt", "nf4_gemm_bnb_mt_workspace_bytes", "nf4_gemm_bnb_mt_swiglu",
            "nf4_gemm_bnb_mt_swiglu_workspace_bytes", "nf4_gemm_bnb_moe", "nf4_gemm_bnb_moe_workspace_bytes",
            "nf4_gemm_bnb_moe_swiglu", "nf4_gemm_bnb_moe_swiglu_workspace_bytes", "nf4_gemm_bnb_moe_down",
-           "nf4_gemm_bnb_moe_down_workspace_bytes")
+           "nf4_gemm_bnb_moe_down_workspace_bytes", "nf4_lora_add", "nf4_lora_add_routed")
 
 
 def load(name):
@@ -68,6 +78,9 @@ def main():
     ap.add_argument("--entries", default="nf4_gemm_ref,nf4_gemm_bnb,nf4_gemm_ref_grouped")
     ap.add_argument("--moe", default="8,14336,4096,2;8,4096,14336,1")
     ap.add_argument("--tokens", default="1,16,64")
+    ap.add_argument("--lora-shapes", default="4096,4096;14336,4096")
+    ap.add_argument("--ranks", default="16,64,128", help="128 is the only way to the 8-r-tile kernels")
+    ap.add_argument("--lora-ms", default="1,16,32,128", help="both row-block heights")
     args = ap.parse_args()
     entries = [e for e in args.entries.split(",") if e]
     names = [args.a, args.b] + ([args.again] if args.again else [])
@@ -85,7 +98,8 @@ def main():
     code2 = torch.linspace(-1.0, 1.0, 256, device=dev)
     off = torch.full((1,), 0.01, device=dev)
 
-    EXACT = ("nf4_gemm_bnb_mt", "nf4_gemm_bnb_mt_swiglu", "nf4_gemm_bnb_moe", "nf4_gemm_bnb_moe_swiglu", "nf4_gemm_bnb_moe_down")
+    EXACT = ("nf4_gemm_bnb_mt", "nf4_gemm_bnb_mt_swiglu", "nf4_gemm_bnb_moe", "nf4_gemm_bnb_moe_swiglu", "nf4_gemm_bnb_moe_down",
+             "nf4_lora_add", "nf4_lora_add_routed")
 
     def report(entry, what, M, n, ts, bit_equal):
         med = [sorted(t)[len(t) // 2] for t in ts]
@@ -101,11 +115,15 @@ def main():
         for L in libs if wsz else ():  # a buffer no split-K ever ran on has nothing to report
             assert L.nf4_gemm_check_workspace(work.data_ptr(), work.numel(), torch.cuda.current_stream().cuda_stream) == 0
 
-    def point(entry, what, M, n, work, wsz, runs, outs):
-        """runs[i]: build i's n launches (the first into outs[i]).  Bit-equal outputs, then the rounds."""
+    def point(entry, what, M, n, work, wsz, runs, outs, start=None):
+        """runs[i]: build i's n launches (the first into outs[i]).  Bit-equal outputs, then the rounds.
+        start: what an in-place entry's outputs begin as."""
         same = True
         for i, (run, out) in enumerate(zip(runs, outs)):
-            out.view(torch.int16).fill_(0x7FFF)  # NaN bits: a row nobody stores is seen
+            if start is None:
+                out.view(torch.int16).fill_(0x7FFF)  # NaN bits: a row nobody stores is seen
+            else:
+                out.copy_(start)
             run()
             torch.cuda.synchronize()
             eq = torch.equal(out.view(torch.int16), outs[0].view(torch.int16))
@@ -173,6 +191,49 @@ def main():
 
                 point("nf4_gemm_bnb_mt_swiglu", f"{n}x{k}", M, copies, work, wsz, [sg(L, h) for L, h in zip(libs, hs)], hs)
             del ws, pairs
+    lora_entries = [e for e in ("nf4_lora_add", "nf4_lora_add_routed") if e in entries]
+    lora_shapes = [tuple(int(v) for v in t.split(",")) for t in args.lora_shapes.split(";") if t]
+    for n, k, r in [(n, k, int(r)) for n, k in lora_shapes for r in args.ranks.split(",")] if lora_entries else ():
+        # 8 stacks of 64 adapters; a routing over S < 64 takes a stack's first S, the dense entry its adapter 37
+        stacks = [((torch.randn((64, r, k), device=dev, generator=gen) / k ** 0.5).to(torch.bfloat16),
+                   (torch.randn((64, n, r), device=dev, generator=gen) / r ** 0.5).to(torch.bfloat16),
+                   0.5 + torch.rand((64,), device=dev, generator=gen)) for _ in range(8)]
+        for M in [int(v) for v in args.lora_ms.split(",")]:
+            x = torch.randn((M, k), device=dev, generator=gen).to(torch.bfloat16)
+            base = torch.randn((M, n), device=dev, generator=gen).to(torch.bfloat16)
+            ys = bf16_out(M, n)
+            what = f"{n}x{k} r={r}"
+
+            def dense(L, y):
+                mats = [(_lib.LoraMat * 1)(_lib.LoraMat(A[37].data_ptr(), B[37].data_ptr(), y.data_ptr(), y.data_ptr(), n, r, 1.25))
+                        for A, B, _ in stacks]
+
+                def run():
+                    sp = torch.cuda.current_stream().cuda_stream
+                    for d in mats:
+                        rc = L.nf4_lora_add(x.data_ptr(), M, k, ctypes.cast(d, ctypes.c_void_p), 1, _lib.BF16, None, sp)
+                        assert rc == 0, rc
+                return run
+
+            def routed(L, y, S, ids):
+                descs = [(_lib.LoraStack * 1)(_lib.LoraStack(A.data_ptr(), B.data_ptr(), sc.data_ptr(), y.data_ptr(), y.data_ptr(), n,
+                                                             r * k, n * r, r)) for A, B, sc in stacks]
+
+                def run():
+                    sp = torch.cuda.current_stream().cuda_stream
+                    for d in descs:
+                        rc = L.nf4_lora_add_routed(x.data_ptr(), ids.data_ptr(), M, k, S, ctypes.cast(d, ctypes.c_void_p), 1, _lib.BF16,
+                                                   None, sp)
+                        assert rc == 0, rc
+                return run
+
+            if "nf4_lora_add" in entries:
+                point("nf4_lora_add", what, M, 8, None, 0, [dense(L, y) for L, y in zip(libs, ys)], ys, start=base)
+            for routing in ("own", "one") if "nf4_lora_add_routed" in entries else ():
+                S, ids = make_routing(routing, M, dev, gen)
+                point("nf4_lora_add_routed", f"{what} {routing} S={S}", M, 8, None, 0,
+                      [routed(L, y, S, ids) for L, y in zip(libs, ys)], ys, start=base)
+        del stacks
     moe_entries = [e for e in ("nf4_gemm_bnb_moe", "nf4_gemm_bnb_moe_swiglu", "nf4_gemm_bnb_moe_down") if e in entries]
     for E, n, k, x_div in [tuple(int(v) for v in s.split(",")) for s in args.moe.split(";") if s] if moe_entries else ():
         copies = max(8, args.budget_mb * (1 << 20) // (E * n * k // 2))

@@ -1,8 +1,9 @@
 """Device assembly and resource usage of the row-tiled GEMM family (nf4_gemm_mt.hip,
-nf4_gemm_mt_swiglu.hip, nf4_gemm_moe.hip, nf4_gemm_moe_swiglu.hip, nf4_gemm_moe_down.hip), and one
-tree's kernels against another's.
+nf4_gemm_mt_swiglu.hip, nf4_gemm_moe.hip, nf4_gemm_moe_swiglu.hip, nf4_gemm_moe_down.hip) or, with
+``--family lora``, of the adapter launches (nf4_lora.hip, nf4_lora_routed.hip), and one tree's
+kernels against another's.
 
-    python tools/gemm_mt_family_asm.py --out DIR [--csrc DIR] [--tables] [--against DIR]
+    python tools/gemm_mt_family_asm.py --out DIR [--family gemm|lora] [--csrc DIR] [--tables] [--against DIR]
 
 Compiles the family's sources of ``--csrc`` (default: this tree's; one that tree lacks is left out)
 to device assembly with the
@@ -14,7 +15,8 @@ directives and renumbering labels, and where they differ scratch, spills, waves 
 AGPRs, the LDS bytes the compiler reports and the v_mfma count; it exits 1 when one of those
 differs.  These kernels' LDS is all dynamic, so the compiler reports 0 and the tables' LDS
 column is the launch's size as the plan headers compute it (`*_lds_bytes`), not a measurement:
-a change of it shows in the plan snapshot tests, not here.
+a change of it shows in the plan snapshot tests, not here.  The adapter launches have no
+resource tables: ``--family lora`` compiles and compares only, kernel by kernel over (DT, MB, RT).
 """
 from __future__ import annotations
 
@@ -45,15 +47,19 @@ FAMILY = {"nf4_gemm_mt": ("gemm_mt", "nf4_gemm_mt_kernel<DT, MT, SM, WV>", 1104)
           "nf4_gemm_moe": ("gemm_moe", "nf4_gemm_moe_kernel<DT, MT, SM, WV> (DOWN = false, W = 1)", 2128),
           "nf4_gemm_moe_swiglu": ("gemm_moe_swiglu", "nf4_gemm_moe_kernel<DT, MT, SM, WV, false, 2> (W = 2: gate and up, SwiGLU)", 3152),
           "nf4_gemm_moe_down": ("gemm_moe_down", "nf4_gemm_moe_kernel<DT, MT, SM, WV, true> (DOWN: the routed sum, W = 1)", 2128)}
+# the adapter launches: source -> the kernel template; 16 instantiations each, no tables
+LORA = {"nf4_lora": "lora_kernel<DT, MB, RT, false> (was nf4_lora_kernel<DT, MB, RT>)",
+        "nf4_lora_routed": "lora_kernel<DT, MB, RT, true> (was nf4_lora_routed_kernel<DT, MB, RT>)"}
+FAMILIES = {"gemm": FAMILY, "lora": LORA}
 FIELDS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch",
           "Occupancy [waves/SIMD]": "waves", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill",
           "LDS Size [bytes/block]": "static_lds"}
 
 
-def compile_all(csrc, out):
+def compile_all(csrc, out, family):
     os.makedirs(out, exist_ok=True)
     procs = []
-    for src in FAMILY:
+    for src in family:
         if not os.path.exists(os.path.join(csrc, src + ".hip")):
             continue
         log = open(os.path.join(out, src + ".log"), "w")
@@ -92,6 +98,12 @@ def kernels(out, src):
 
 
 def params(name):
+    """The leading template parameters of a mangled kernel name: (DT, MT, SM, WV), or (DT, MB, RT)
+    of an adapter kernel.  A kernel that was renamed or gained parameters behind these still maps
+    to its parent by them."""
+    lora = re.search(r"lora\w*kernelILi(\d+)ELi(\d+)ELi(\d+)E", name)
+    if lora:
+        return tuple(int(v) for v in lora.groups())
     dt, mt, sm, wv = (int(v) for v in re.search(r"kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E", name).groups())
     return dt, mt, sm, wv
 
@@ -120,15 +132,16 @@ def write_table(out, src):
         f.write("\n".join(rows) + "\n")
 
 
-def compare(out, base):
+def compare(out, base, family):
     bad = 0
-    for src in FAMILY:
+    what, count = ("DT,MB,RT", 16) if family is LORA else ("DT,MT,SM,WV", 32)
+    for src in family:
         if not os.path.exists(os.path.join(base, src + ".s")):
             print(f"{src}: not in the other tree")
             continue
         # by template parameters: a parameter added behind them changes the mangled names
         new, old = ({params(n): k for n, k in kernels(d, src).items()} for d in (out, base))
-        assert sorted(new) == sorted(old) and len(new) == 32, (src, len(new), len(old))
+        assert sorted(new) == sorted(old) and len(new) == count, (src, len(new), len(old))
         same = 0
         for name in sorted(new):
             n, o = new[name], old[name]
@@ -138,7 +151,7 @@ def compare(out, base):
             mf = [sum(i.startswith("v_mfma") for i in k["insts"]) for k in (n, o)]
             keep = all(n[f] == o[f] for f in ("scratch", "sgpr_spill", "vgpr_spill", "waves", "agprs", "static_lds")) and mf[0] == mf[1]
             bad += not keep
-            print(f"{src} DT,MT,SM,WV={name}: streams differ ({len(o['insts'])} -> {len(n['insts'])} instructions); "
+            print(f"{src} {what}={name}: streams differ ({len(o['insts'])} -> {len(n['insts'])} instructions); "
                   f"VGPRs {o['vgprs']} -> {n['vgprs']}, SGPRs {o['sgprs']} -> {n['sgprs']}, AGPRs {o['agprs']} -> {n['agprs']}, "
                   f"scratch {o['scratch']} -> {n['scratch']}, spills {o['sgpr_spill'] + o['vgpr_spill']} -> "
                   f"{n['sgpr_spill'] + n['vgpr_spill']}, waves/SIMD {o['waves']} -> {n['waves']}, v_mfma {mf[1]} -> {mf[0]}"
@@ -151,17 +164,21 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--csrc", default=os.path.join(PKG, "csrc"))
     ap.add_argument("--out", required=True)
+    ap.add_argument("--family", default="gemm", choices=sorted(FAMILIES))
     ap.add_argument("--tables", action="store_true")
     ap.add_argument("--against", default="")
     ap.add_argument("--no-compile", action="store_true", help="--out already holds the .s and .log files")
     args = ap.parse_args()
+    family = FAMILIES[args.family]
     if not args.no_compile:
-        compile_all(args.csrc, args.out)
+        compile_all(args.csrc, args.out, family)
+    if args.tables and family is LORA:
+        sys.exit("--tables: the adapter launches have no resource tables")
     if args.tables:
         for src in FAMILY:
             if os.path.exists(os.path.join(args.out, src + ".s")):
                 write_table(args.out, src)
-    if args.against and compare(args.out, args.against):
+    if args.against and compare(args.out, args.against, family):
         sys.exit(1)
 
 
