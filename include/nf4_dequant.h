@@ -527,6 +527,36 @@ int nf4_gemm_bnb_moe(const void* x, const void* expert_ids, int64_t P, int32_t x
                      void* y, int32_t out_dtype, void* workspace, size_t workspace_bytes,
                      const nf4_gemm_cfg* cfg, void* hip_stream);
 
+/* nf4_gemm_bnb_moe beyond 128 pairs: the same product, descriptor, rules, alignments, order of
+ * status codes and workspace contract for 1 <= P <= NF4DQ_MOE_RB_MAX_PAIRS (token, choice) pairs
+ * in ONE launch -- a decode batch of 32 sequences at top-8, a speculative verify step, a short
+ * prompt.  The ids are still read on the device only, so the call is capturable and a replay
+ * follows the router.  The grid is experts x column tiles x K slices x ceil(P / 128) row blocks,
+ * fixed by the host whatever the routing: a workgroup lists its expert's pairs in ascending order
+ * by ballots over all P ids and owns entries [128 rb, 128 rb + 128) of that list; one whose
+ * expert has no more than 128 rb pairs returns before any weight or statistics load.  An expert's
+ * weight is therefore read once per row block it fills, an idle expert's never.  A row's fp32 sum
+ * depends on the chunk order and the K slices alone, so every row's bits are those
+ * nf4_gemm_bnb_moe stores for that row at the cfg with the same waves and ksplit, and for
+ * P <= 128 the two entries' outputs are equal bit for bit.
+ * P > NF4DQ_MOE_RB_MAX_PAIRS: NF4DQ_ERR_SHAPE; P == 0: NF4DQ_OK, nothing launched.  More split-K
+ * tickets (experts * column tiles * row blocks) than the workspace header holds, or K slices
+ * whose slab (ksplit * P * N floats) reaches 2^32 bytes: NF4DQ_ERR_TOO_LARGE.
+ * cfg NULL = the library's choice from (P, experts, N, K, CU count) alone.  A cfg names kernel
+ * NF4DQ_GEMM_MOE_RB (0 = the same) with nf4_gemm_bnb_moe's fields and never falls back: an invalid
+ * one, NF4DQ_GEMM_MOE included, is NF4DQ_ERR_ARG.
+ * Workspace (nf4_gemm_bnb_moe_rb_workspace_bytes; 0 = none, one K slice): nf4_gemm_bnb_moe's
+ * layout and contract -- the ticket header, then ksplit slabs of P * N floats indexed by pair, all
+ * zero between calls, shareable with the other fused entries on the same stream.  One ticket per
+ * (expert, column tile, row block); no workgroup waits for another.
+ * Asynchronous on `hip_stream`; one launch; allocates nothing; capturable in a graph. */
+#define NF4DQ_MOE_RB_MAX_PAIRS 1024
+#define NF4DQ_GEMM_MOE_RB 13
+size_t nf4_gemm_bnb_moe_rb_workspace_bytes(int64_t P, const void* experts, const nf4_gemm_cfg* cfg);
+int nf4_gemm_bnb_moe_rb(const void* x, const void* expert_ids, int64_t P, int32_t x_div, const void* experts,
+                        void* y, int32_t out_dtype, void* workspace, size_t workspace_bytes,
+                        const nf4_gemm_cfg* cfg, void* hip_stream);
+
 /* The first half of a Llama-family MLP, `silu(gate(x)) * up(x)`, in bitsandbytes semantics for
  * 1..128 rows: ONE launch of the row-tiled family over the gate and the up weight, which share
  * x and the shape [I][K].  With dt = out_dtype (fp16 / bf16) and rn = round-to-nearest-even to dt,

@@ -82,8 +82,10 @@ GEMM_MOE = 9  # the expert GEMM of a mixture-of-experts block (nf4_gemm_bnb_moe)
 GEMM_MT_SWIGLU = 10  # the fused gate/up SwiGLU launch (nf4_gemm_bnb_mt_swiglu); its own entry only
 GEMM_MOE_SWIGLU = 11  # the fused expert SwiGLU launch (nf4_gemm_bnb_moe_swiglu); its own entry only
 GEMM_MOE_DOWN = 12  # the fused expert down projection with the routed sum (nf4_gemm_bnb_moe_down); its own entry only
+GEMM_MOE_RB = 13  # the expert GEMM in row blocks, up to MOE_RB_MAX_PAIRS pairs (nf4_gemm_bnb_moe_rb); its own entry only
 ACT_SILU = 0  # NF4DQ_ACT_SILU: the activation of nf4_gemm_bnb_mt_swiglu and nf4_gemm_bnb_moe_swiglu
 MOE_MAX_PAIRS = 128    # NF4DQ_MOE_MAX_PAIRS: (token, choice) pairs of one nf4_gemm_bnb_moe launch
+MOE_RB_MAX_PAIRS = 1024  # NF4DQ_MOE_RB_MAX_PAIRS: (token, choice) pairs of one nf4_gemm_bnb_moe_rb launch
 MOE_MAX_EXPERTS = 256  # NF4DQ_MOE_MAX_EXPERTS
 
 
@@ -206,6 +208,9 @@ SIGNATURES = {
     "nf4_gemm_bnb_moe_workspace_bytes": (ctypes.c_size_t, [_I64, _P, ctypes.POINTER(GemmCfg)]),
     "nf4_gemm_bnb_moe": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _I32, _P, ctypes.c_size_t,
                                         ctypes.POINTER(GemmCfg), _P]),
+    "nf4_gemm_bnb_moe_rb_workspace_bytes": (ctypes.c_size_t, [_I64, _P, ctypes.POINTER(GemmCfg)]),
+    "nf4_gemm_bnb_moe_rb": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _I32, _P, ctypes.c_size_t,
+                                           ctypes.POINTER(GemmCfg), _P]),
     # `gate_up`: const void* in the header, pointing at GemmBnbMat[2] (gate, up)
     "nf4_gemm_bnb_mt_swiglu_workspace_bytes": (ctypes.c_size_t, [_I64, _I64, _I64, ctypes.POINTER(GemmCfg)]),
     "nf4_gemm_bnb_mt_swiglu": (ctypes.c_int, [_P, _I64, _I64, _P, _I32, _I32, _P, _I32, _P, ctypes.c_size_t,

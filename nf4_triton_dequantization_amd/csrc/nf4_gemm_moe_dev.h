@@ -1,14 +1,17 @@
 // nf4_gemm_moe_dev.h -- the device code of the fused NF4 expert kernels of a mixture-of-experts
-// block in bitsandbytes semantics, once.  Three launchers instantiate this one kernel template:
+// block in bitsandbytes semantics, once.  Four launchers instantiate this one kernel template:
 //  * nf4_gemm_moe.hip (nf4_gemm_bnb_moe: the products of the (token, choice) pairs): DOWN false,
 //    W = 1;
 //  * nf4_gemm_moe_down.hip (nf4_gemm_bnb_moe_down: the same products, combined per token with the
 //    routing weights inside the launch): DOWN true, W = 1;
 //  * nf4_gemm_moe_swiglu.hip (nf4_gemm_bnb_moe_swiglu: h = silu(g) * u over a gate and an up stack):
-//    DOWN false, W = 2.
-// DOWN and W are compile-time: every branch of the other instantiations is discarded.  What the
+//    DOWN false, W = 2;
+//  * nf4_gemm_moe_rb.hip (nf4_gemm_bnb_moe_rb: nf4_gemm_bnb_moe's products for up to 1024 pairs,
+//    in row blocks of 128 listed rows): DOWN false, W = 1, RB true.
+// DOWN, W and RB are compile-time: every branch of the other instantiations is discarded.  What the
 // merge of the three kernels into this template moved in the generated code, and what it cost, is
-// in profiles/gemm_moe_family/README.md.
+// in profiles/gemm_moe_family/README.md; that RB left every earlier instantiation's instruction
+// stream as it was, and what that took, is in profiles/gemm_moe_rb/README.md.
 //
 // y[p][N] = x[p / x_div][K] . W_e[N][K]^T with e = expert_ids[p] read ON THE DEVICE and W_e the
 // 16-bit weights nf4_dequant_bnb writes for expert e, bit for bit.  One launch covers every
@@ -38,6 +41,15 @@
 //    to exactly one expert: stored once per column tile, directly or by the reducer.
 // Split-K: the row-tiled kernel's hand-off with the slab indexed by pair and one ticket per
 // (expert, column tile).  Nobody waits for anybody: there is no poll.
+//
+// RB: the grid gains ceil(P / 128) row blocks (the outermost index).  A workgroup ballots all P ids
+// in rounds of 64, one per lane, with a running count, and owns entries [128 rb, 128 rb + 128) of
+// its expert's ascending pair list: wave 0 writes only those to the LDS list, which stays 128
+// entries.  A workgroup whose expert has no more than 128 rb pairs returns before any weight or
+// statistics load and draws no ticket; tickets are one per (expert, column tile, row block); rows
+// of invalid ids are zeroed by the workgroups of expert 0, K slice 0, row block 0 over all P.
+// Everything behind the list -- gather, stage, decode, MFMA, scatter, hand-off, reducer -- is the
+// code above on the block's rows, so a row's bits do not depend on the entry that computed it.
 //
 // W: what a wave's two strips are (MtStrips<W>) and what becomes of their sums.  All of the above
 // holds for both.
@@ -195,9 +207,10 @@ __device__ __forceinline__ const MoeArgsT<1>& moe_gemm_args(const MoeDownArgs& a
 // each has the order of the kernel it was merged from: with one order for both, the other's
 // instruction streams move and the 128-pair SwiGLU launch measured up to 1 % slower,
 // profiles/gemm_moe_family/README.md)
-template <int DT, int MT, int SM, int WV, bool DOWN = false, int W = 1>
+template <int DT, int MT, int SM, int WV, bool DOWN = false, int W = 1, bool RB = false>
 __global__ __launch_bounds__(64 * WV, MT <= 2 ? 2 : 1) void nf4_gemm_moe_kernel(const MoeKernArgs<DOWN, W> KA) {
     static_assert(!DOWN || W == 1, "the routed sum is behind one stack's products");
+    static_assert(!RB || (!DOWN && W == 1), "row blocks: the plain expert GEMM alone");
     using Strips = MtStrips<W>;
     using Out = std::conditional_t<W == 2, SgOut<DT>, MtSumOut<DT>>;
     const MoeArgsT<W>& A = moe_gemm_args(KA);
@@ -216,51 +229,96 @@ __global__ __launch_bounds__(64 * WV, MT <= 2 ? 2 : 1) void nf4_gemm_moe_kernel(
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t nl = lane & 15u, kh = lane >> 4;
     const uint32_t ks = blockIdx.x % A.ksplit, et = blockIdx.x / A.ksplit;
-    const uint32_t tile = et % A.tiles, ex = et / A.tiles;
+    // (RB: et = (row block * E + expert) * tiles + tile, which is also the ticket's index)
+    const uint32_t tile = et % A.tiles, ex = RB ? et / A.tiles % A.E : et / A.tiles;
 
-    // the routing: every wave reads all P ids (in-bounds repeats past P) and ballots
-    const uint32_t p0 = lane, p1 = lane + 64u;
-    const int32_t id0 = A.ids[p0 < A.P ? p0 : A.P - 1u], id1 = A.ids[p1 < A.P ? p1 : A.P - 1u];
-    const bool in0 = p0 < A.P, in1 = p1 < A.P;
-    const uint64_t m0 = __ballot(in0 && id0 == (int32_t)ex), m1 = __ballot(in1 && id1 == (int32_t)ex);
-    const uint32_t cnt0 = (uint32_t)__popcll(m0), cnt = cnt0 + (uint32_t)__popcll(m1);
+    // the routing up to 128 pairs (!RB): every wave reads all P ids (in-bounds repeats past P), two
+    // per lane, and ballots.  (Declared here and filled ahead of `arrive`, where the kernels this
+    // template was merged from had them: with the statements in another order the DOWN
+    // instantiations' instruction streams move, profiles/gemm_moe_rb/README.md)
+    uint32_t p0, p1, cnt0;
+    int32_t id0, id1;
+    bool in0, in1;
+    uint64_t m0, m1;
+    uint32_t cnt;  // the rows this workgroup stages: the expert's pairs, or (RB) its pairs in this row block
+    if constexpr (!RB) {
+        p0 = lane, p1 = lane + 64u;
+        id0 = A.ids[p0 < A.P ? p0 : A.P - 1u], id1 = A.ids[p1 < A.P ? p1 : A.P - 1u];
+        in0 = p0 < A.P, in1 = p1 < A.P;
+        m0 = __ballot(in0 && id0 == (int32_t)ex), m1 = __ballot(in1 && id1 == (int32_t)ex);
+        cnt0 = (uint32_t)__popcll(m0), cnt = cnt0 + (uint32_t)__popcll(m1);
+    }
 
     // DOWN: this expert's arrival at the tile's ticket; the last of the E arrivals combines the tile
     auto arrive = [&]() {
         if constexpr (DOWN)
             if (mt_publish_last(KA.c.tile_ticket + tile, A.E, flag)) moe_combine<DT, T, COLS>(KA.c, tile * COLS);
     };
-    if constexpr (DOWN) {
-        if (cnt == 0u) {  // an idle expert: no weight, no statistics; slice 0 arrives for it
-            if (ks == 0u) arrive();
-            return;
-        }
-    }
-    if (!DOWN && ex == 0u && ks == 0u) {  // rows of ids outside [0, E): zeros in this tile's columns
-        const uint64_t z0 = __ballot(in0 && (uint32_t)id0 >= A.E), z1 = __ballot(in1 && (uint32_t)id1 >= A.E);
-        for (int h = 0; h < 2; ++h)
-            for (uint64_t b = h ? z1 : z0; b; b &= b - 1u) {
-                const uint32_t p = (uint32_t)__builtin_ctzll(b) + 64u * (uint32_t)h;
-                if (tid < COLS / 4u)
-                    *reinterpret_cast<u32x2*>(reinterpret_cast<uint16_t*>(A.y) + (p * A.N + tile * COLS + 4u * tid)) = u32x2{0u, 0u};
+    if constexpr (RB) {
+        // Row blocks: up to NF4DQ_MOE_RB_MAX_PAIRS ids in rounds of 64 (in-bounds repeats past P),
+        // one wave-uniform mask a round and a running count; the workgroup owns entries
+        // [lo, lo + 128) of the expert's ascending pair list and writes only those to LDS.
+        const uint32_t lo = NF4DQ_MOE_MAX_PAIRS * (et / A.tiles / A.E);
+        if (lo == 0u && ex == 0u && ks == 0u) {  // rows of ids outside [0, E), over all P: zeros in this tile's columns
+            for (uint32_t base = 0; base < A.P; base += 64u) {
+                const uint32_t p = base + lane;
+                const int32_t id = A.ids[p < A.P ? p : A.P - 1u];
+                for (uint64_t b = __ballot(p < A.P && (uint32_t)id >= A.E); b; b &= b - 1u) {
+                    const uint32_t pz = base + (uint32_t)__builtin_ctzll(b);
+                    if (tid < COLS / 4u)
+                        *reinterpret_cast<u32x2*>(reinterpret_cast<uint16_t*>(A.y) + (pz * A.N + tile * COLS + 4u * tid)) = u32x2{0u, 0u};
+                }
             }
-    }
-    if (cnt == 0u) return;  // an idle expert: no weight, no statistics, no ticket
-
-    if (wave == 0u) {  // the expert's ascending pair list, by popcount prefix
+        }
         const uint64_t below = (uint64_t(1) << lane) - 1u;
-        if ((m0 >> lane) & 1u) {
-            const uint32_t r = (uint32_t)__popcll(m0 & below);
-            prow[r] = p0;
-            srow[r] = p0 / A.x_div;
+        uint32_t seen = 0;  // the expert's pairs below `base`
+        for (uint32_t base = 0; base < A.P && seen < lo + NF4DQ_MOE_MAX_PAIRS; base += 64u) {
+            const uint32_t p = base + lane;
+            const int32_t id = A.ids[p < A.P ? p : A.P - 1u];
+            const uint64_t m = __ballot(p < A.P && id == (int32_t)ex);
+            const uint32_t r = seen + (uint32_t)__popcll(m & below) - lo;  // the pair's entry in this block, if it has one
+            if (wave == 0u && ((m >> lane) & 1u) && r < (uint32_t)NF4DQ_MOE_MAX_PAIRS) {
+                prow[r] = p;
+                srow[r] = p / A.x_div;
+            }
+            seen += (uint32_t)__popcll(m);
         }
-        if ((m1 >> lane) & 1u) {
-            const uint32_t r = cnt0 + (uint32_t)__popcll(m1 & below);
-            prow[r] = p1;
-            srow[r] = p1 / A.x_div;
+        // an idle expert, or a row block past its pairs: no weight, no statistics, no ticket
+        if (seen <= lo) return;
+        cnt = seen - lo < (uint32_t)NF4DQ_MOE_MAX_PAIRS ? seen - lo : (uint32_t)NF4DQ_MOE_MAX_PAIRS;
+    } else {
+        if constexpr (DOWN) {
+            if (cnt == 0u) {  // an idle expert: no weight, no statistics; slice 0 arrives for it
+                if (ks == 0u) arrive();
+                return;
+            }
+        }
+        if (!DOWN && ex == 0u && ks == 0u) {  // rows of ids outside [0, E): zeros in this tile's columns
+            const uint64_t z0 = __ballot(in0 && (uint32_t)id0 >= A.E), z1 = __ballot(in1 && (uint32_t)id1 >= A.E);
+            for (int h = 0; h < 2; ++h)
+                for (uint64_t b = h ? z1 : z0; b; b &= b - 1u) {
+                    const uint32_t p = (uint32_t)__builtin_ctzll(b) + 64u * (uint32_t)h;
+                    if (tid < COLS / 4u)
+                        *reinterpret_cast<u32x2*>(reinterpret_cast<uint16_t*>(A.y) + (p * A.N + tile * COLS + 4u * tid)) = u32x2{0u, 0u};
+                }
+        }
+        if (cnt == 0u) return;  // an idle expert: no weight, no statistics, no ticket
+
+        if (wave == 0u) {  // the expert's ascending pair list, by popcount prefix
+            const uint64_t below = (uint64_t(1) << lane) - 1u;
+            if ((m0 >> lane) & 1u) {
+                const uint32_t r = (uint32_t)__popcll(m0 & below);
+                prow[r] = p0;
+                srow[r] = p0 / A.x_div;
+            }
+            if ((m1 >> lane) & 1u) {
+                const uint32_t r = cnt0 + (uint32_t)__popcll(m1 & below);
+                prow[r] = p1;
+                srow[r] = p1 / A.x_div;
+            }
         }
     }
-    const uint32_t my_tiles = (cnt + 15u) >> 4;  // row tiles this expert fills
+    const uint32_t my_tiles = (cnt + 15u) >> 4;  // row tiles this expert (RB: this row block) fills
 
     const uint32_t col0 = tile * COLS + wave * Strips::kWaveCols;
     const uint32_t c_begin = ks * A.cps < A.chunks ? ks * A.cps : A.chunks;

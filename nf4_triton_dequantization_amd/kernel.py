@@ -972,11 +972,12 @@ def _moe_args(name: str, x: torch.Tensor, experts, expert_ids: torch.Tensor):
     return T, k, x_div, x3
 
 
-def _moe_fusable(x: torch.Tensor, experts, P: int) -> bool:
-    """The fused-route conditions of the expert entries on one ``Experts4bit`` (nf4_moe_linear_bnb's docstring)."""
+def _moe_fusable(x: torch.Tensor, experts, P: int, max_pairs: int = _lib.MOE_MAX_PAIRS) -> bool:
+    """The fused-route conditions of the expert entries on one ``Experts4bit`` (nf4_moe_linear_bnb's docstring);
+    ``max_pairs``: the entry's pair bound."""
     N, K, E = int(experts.out_features), int(experts.in_features), int(experts.num_experts)
     q = experts.weight.data
-    return (q.device.type == "cuda" and experts.dtype in (torch.float16, torch.bfloat16) and 1 <= P <= _lib.MOE_MAX_PAIRS
+    return (q.device.type == "cuda" and experts.dtype in (torch.float16, torch.bfloat16) and 1 <= P <= max_pairs
             and N % 64 == 0 and N >= 64 and K % 128 == 0 and K >= 128 and 1 <= E <= _lib.MOE_MAX_EXPERTS
             and int(experts.blocksize) == 64 and q.dtype == torch.uint8 and q.is_contiguous()
             and q.data_ptr() % 16 == 0 and (N * K // 2) % 16 == 0
@@ -1009,6 +1010,16 @@ def _moe_desc(experts) -> "_lib.MoeExperts":
                            N, K, E, 1, 64, 0)
 
 
+# (token, choice) pairs at which nf4_moe_linear_bnb takes the row-block launch (nf4_gemm_bnb_moe_rb)
+# in place of nf4_gemm_bnb_moe, whose domain ends at MOE_MAX_PAIRS.  The range is the entry's
+# CAPABILITY, as 1 .. MOE_MAX_PAIRS is nf4_gemm_bnb_moe's, not a measured win: past 128 pairs the
+# alternative is the per-expert loop, which synchronises with the host once per expert and cannot be
+# captured in a graph at all.  What the launch costs against that loop in its best case and against
+# ceil(P / 128) nf4_gemm_bnb_moe launches is in profiles/gemm_moe_rb/ (tools/bench_moe_rb.py).
+MOE_RB_ROUTED_MIN_P = 129
+MOE_RB_ROUTED_MAX_P = 1024
+
+
 def nf4_moe_linear_bnb(x: torch.Tensor, experts, expert_ids: torch.Tensor,
                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One projection of a mixture-of-experts block for all experts, in bitsandbytes semantics:
@@ -1022,12 +1033,15 @@ def nf4_moe_linear_bnb(x: torch.Tensor, experts, expert_ids: torch.Tensor,
     outside ``0..E-1`` gets a row of zeros, as ``nf4_embedding_bnb`` treats an id outside the
     table; one token may name the same expert twice.
 
-    The fused route -- GPU tensors, fp16 / bf16, ``1 <= T*k <= MOE_MAX_PAIRS``, N % 64 == 0,
-    K % 128 == 0 and no gradient being recorded for ``x`` -- is ONE launch
-    (``nf4_gemm_bnb_moe``) plus at most a cast of the ids to int32: the ids and the offsets are
+    The fused route -- GPU tensors, fp16 / bf16, ``1 <= T*k <= MOE_RB_ROUTED_MAX_P``, N % 64 == 0,
+    K % 128 == 0 and no gradient being recorded for ``x`` -- is ONE launch plus at most a cast of
+    the ids to int32: ``nf4_gemm_bnb_moe`` up to ``MOE_MAX_PAIRS`` pairs, ``nf4_gemm_bnb_moe_rb``
+    (the same kernel over row blocks of 128 of an expert's pairs) for ``MOE_RB_ROUTED_MIN_P <= T*k
+    <= MOE_RB_ROUTED_MAX_P``.  The ids and the offsets are
     read on the device, never by the host, so ``torch.cuda.graph`` captures the call and a replay
     follows whatever the router wrote into ``expert_ids`` since.  An expert without a pair costs
-    no weight traffic.  Everything else (more pairs, CPU tensors, a gradient for ``x``) takes the
+    no weight traffic.  Everything else (more than ``MOE_RB_ROUTED_MAX_P`` pairs, CPU tensors, a
+    gradient for ``x``) takes the
     per-expert loop over ``nf4_linear_bnb(x[idx], experts.expert(e))``, which SYNCHRONISES with
     the host once per expert (it reads the routing back) and is therefore not capturable; autograd
     follows it to ``x``.  Both routes use the same weights and fp32 accumulation; the summation
@@ -1044,18 +1058,21 @@ def nf4_moe_linear_bnb(x: torch.Tensor, experts, expert_ids: torch.Tensor,
     P = T * k
     if P == 0:
         return out
-    if not _moe_fusable(x, experts, P):
+    row_blocks = MOE_RB_ROUTED_MIN_P <= P <= MOE_RB_ROUTED_MAX_P
+    if not _moe_fusable(x, experts, P, _lib.MOE_RB_MAX_PAIRS if row_blocks else _lib.MOE_MAX_PAIRS):
         return _moe_fallback(x3, experts, expert_ids, out)
     xc, ids = _moe_operands(x, expert_ids, dtype)
     desc = _moe_desc(experts)
     L = _lib.lib()
+    size, entry = ((L.nf4_gemm_bnb_moe_rb_workspace_bytes, L.nf4_gemm_bnb_moe_rb) if row_blocks
+                   else (L.nf4_gemm_bnb_moe_workspace_bytes, L.nf4_gemm_bnb_moe))
     dp = ctypes.cast(ctypes.pointer(desc), ctypes.c_void_p)
     with torch.cuda.device(dev):
-        ws_bytes = L.nf4_gemm_bnb_moe_workspace_bytes(P, dp, None)
+        ws_bytes = size(P, dp, None)
         ws = _gemm_workspace(dev, ws_bytes) if ws_bytes else None
-        rc = L.nf4_gemm_bnb_moe(xc.data_ptr(), ids.data_ptr(), P, x_div, dp, out.data_ptr(), _dtype_code(dtype),
-                                ws.data_ptr() if ws is not None else None, ws_bytes, None,
-                                torch.cuda.current_stream().cuda_stream)
+        rc = entry(xc.data_ptr(), ids.data_ptr(), P, x_div, dp, out.data_ptr(), _dtype_code(dtype),
+                   ws.data_ptr() if ws is not None else None, ws_bytes, None,
+                   torch.cuda.current_stream().cuda_stream)
     _lib.check(rc, "nf4 fused moe gemm")
     return out
 
@@ -1217,8 +1234,9 @@ def nf4_moe_swiglu_bnb(x: torch.Tensor, gate_experts, up_experts, expert_ids: to
     synchronises with the host and ``torch.cuda.graph`` captures the call.  It is taken under
     ``nf4_moe_linear_bnb``'s fused-route conditions on both stacks and
     ``MOE_SWIGLU_ROUTED_MIN_P <= T*k <= MOE_SWIGLU_ROUTED_MAX_P``.  Everything else -- other pair
-    counts, more than ``MOE_MAX_PAIRS`` pairs, CPU tensors, a gradient being recorded for ``x``
-    -- is the expression above, which has the same definition and which autograd follows; the
+    counts, CPU tensors, a gradient being recorded for ``x`` -- is the expression above, which has
+    the same definition and which autograd follows (up to ``MOE_RB_ROUTED_MAX_P`` pairs its two
+    ``nf4_moe_linear_bnb`` calls are fused launches themselves, so it stays capturable); the
     GEMMs' summation order may differ between the routes, so the last bit of ``g`` and ``u`` may.
     """
     I, K, E = int(gate_experts.out_features), int(gate_experts.in_features), int(gate_experts.num_experts)

@@ -1,5 +1,5 @@
 """Device assembly and resource usage of the row-tiled GEMM family (nf4_gemm_mt.hip,
-nf4_gemm_mt_swiglu.hip, nf4_gemm_moe.hip, nf4_gemm_moe_swiglu.hip, nf4_gemm_moe_down.hip) or, with
+nf4_gemm_mt_swiglu.hip, nf4_gemm_moe.hip, nf4_gemm_moe_rb.hip, nf4_gemm_moe_swiglu.hip, nf4_gemm_moe_down.hip) or, with
 ``--family lora``, of the adapter launches (nf4_lora.hip, nf4_lora_routed.hip), and one tree's
 kernels against another's.
 
@@ -8,7 +8,7 @@ kernels against another's.
 Compiles the family's sources of ``--csrc`` (default: this tree's; one that tree lacks is left out)
 to device assembly with the
 Makefile's flags (``--cuda-device-only -S -Rpass-analysis=kernel-resource-usage``, without
--Werror) into ``--out``.  ``--tables`` rewrites profiles/gemm_{mt,mt_swiglu,moe,moe_swiglu,moe_down}/resource_usage.txt
+-Werror) into ``--out``.  ``--tables`` rewrites profiles/gemm_{mt,mt_swiglu,moe,moe_rb,moe_swiglu,moe_down}/resource_usage.txt
 from the compiler's remarks.  ``--against DIR`` (an ``--out`` of another tree, e.g. the parent
 commit's sources) compares kernel by kernel: the instruction streams after dropping comments and
 directives and renumbering labels, and where they differ scratch, spills, waves per SIMD,
@@ -45,6 +45,7 @@ FLAGS = makefile_flags()
 FAMILY = {"nf4_gemm_mt": ("gemm_mt", "nf4_gemm_mt_kernel<DT, MT, SM, WV>", 1104),
           "nf4_gemm_mt_swiglu": ("gemm_mt_swiglu", "nf4_gemm_mt_swiglu_kernel<DT, MT, SM, WV>", 2128),
           "nf4_gemm_moe": ("gemm_moe", "nf4_gemm_moe_kernel<DT, MT, SM, WV> (DOWN = false, W = 1)", 2128),
+          "nf4_gemm_moe_rb": ("gemm_moe_rb", "nf4_gemm_moe_kernel<DT, MT, SM, WV, false, 1, true> (RB: row blocks of 128 listed rows, W = 1)", 2128),
           "nf4_gemm_moe_swiglu": ("gemm_moe_swiglu", "nf4_gemm_moe_kernel<DT, MT, SM, WV, false, 2> (W = 2: gate and up, SwiGLU)", 3152),
           "nf4_gemm_moe_down": ("gemm_moe_down", "nf4_gemm_moe_kernel<DT, MT, SM, WV, true> (DOWN: the routed sum, W = 1)", 2128)}
 # the adapter launches: source -> the kernel template; 16 instantiations each, no tables
