@@ -92,8 +92,10 @@ def _on_device(device: torch.device, *tensors: torch.Tensor) -> None:
                                f"all of them must be on the same ROCm device")
 
 
-def _stream_ptr(device: torch.device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
+def _two_devices(a, b) -> RuntimeError:
+    # what `x @ W.t()` raises for tensors on different devices
+    return RuntimeError(f"Expected all tensors to be on the same device, but found at least two devices, "
+                        f"{a} and {b}!")
 
 
 def _as_u8_flat(q: torch.Tensor) -> torch.Tensor:
@@ -115,35 +117,38 @@ def _prepare(module):
     return qweight, absmax, absmax32, dtype, m, n
 
 
-def _flat_ptr(t: torch.Tensor) -> tuple:
-    """(tensor kept alive, data pointer, numel) of a contiguous view; copies only when needed."""
-    if not t.is_contiguous():
-        t = t.contiguous()
-    return t, t.data_ptr(), t.numel()
+def _operand(t: torch.Tensor, dtype, keep: list) -> tuple:
+    """(data pointer, numel) of ``t`` as a contiguous tensor of ``dtype`` (None: its own).  A cast or
+    copy made for that goes to ``keep``, which the caller holds until the entry has returned."""
+    c = t if dtype is None or t.dtype == dtype else t.to(dtype)
+    if not c.is_contiguous():
+        c = c.contiguous()
+    if c is not t:
+        keep.append(c)
+    return c.data_ptr(), c.numel()
+
+
+def _ref_stats(absmax: torch.Tensor, absmax32: torch.Tensor, keep: list) -> tuple:
+    """The statistics operands in reference semantics, ``(ap, an, bp, bn)``: uint8 absmax as it is,
+    absmax32 cast to fp32 (:182); an empty one raises as the reference's ceil(total / 0) does (:175, :184)."""
+    ap, an = _operand(absmax, None, keep)
+    bp, bn = _operand(absmax32, torch.float32, keep)
+    if an == 0 or bn == 0:
+        raise ZeroDivisionError("integer division or modulo by zero (empty absmax)")
+    return ap, an, bp, bn
 
 
 def _launch(qweight, absmax, absmax32, out, m, n, code, stream) -> None:
     """Casts of kernel_optimized.py:162-186 and one C-ABI call on `stream`."""
-    if qweight.dtype != torch.uint8:
-        qweight = qweight.to(torch.uint8)  # value cast, as :162-163
-    qweight, qp, qn = _flat_ptr(qweight)
+    keep = []
+    qp, qn = _operand(qweight, torch.uint8, keep)  # value cast, as :162-163
     _on_device(qweight.device, absmax, absmax32 if absmax.dtype == torch.uint8 else absmax)
     L = _lib.lib()
     if absmax.dtype == torch.uint8:
-        if absmax32.dtype != torch.float32:
-            absmax32 = absmax32.to(torch.float32)  # :182
-        absmax, ap, an = _flat_ptr(absmax)
-        absmax32, bp, bn = _flat_ptr(absmax32)
-        if an == 0 or bn == 0:
-            # reference: repeats = ceil(total / 0) -> ZeroDivisionError (:175, :184)
-            raise ZeroDivisionError("integer division or modulo by zero (empty absmax)")
-        rc = L.nf4_dequant_ref(qp, qn, ap, an, bp, bn, out.data_ptr(), code, m, n, stream)
+        rc = L.nf4_dequant_ref(qp, qn, *_ref_stats(absmax, absmax32, keep), out.data_ptr(), code, m, n, stream)
     else:
         # single-quant branch (:166-167 -> :273-274): absmax.view(m, -1)[:, :bpr].to(float32)
-        if absmax.dtype != torch.float32:
-            absmax = absmax.to(torch.float32)
-        absmax, ap, an = _flat_ptr(absmax)
-        rc = L.nf4_dequant_single(qp, qn, ap, an, out.data_ptr(), code, m, n, stream)
+        rc = L.nf4_dequant_single(qp, qn, *_operand(absmax, torch.float32, keep), out.data_ptr(), code, m, n, stream)
     if rc:
         _lib.check(rc, "nf4 dequantize")
 
@@ -169,24 +174,15 @@ def _launch_cpu(qweight, absmax, absmax32, out, m, n, code) -> None:
         if t.device.type != "cpu":
             raise RuntimeError(f"NF4 quant state tensor on '{t.device}', packed weight on the host: "
                                f"all of them must be on the same device")
-    if qweight.dtype != torch.uint8:
-        qweight = qweight.to(torch.uint8)  # value cast, as :162-163
-    qweight, qp, qn = _flat_ptr(qweight)
+    keep = []
+    qp, qn = _operand(qweight, torch.uint8, keep)  # value cast, as :162-163
     L = _lib.lib()
     threads = cpu_threads()
     if absmax.dtype == torch.uint8:
-        if absmax32.dtype != torch.float32:
-            absmax32 = absmax32.to(torch.float32)  # :182
-        absmax, ap, an = _flat_ptr(absmax)
-        absmax32, bp, bn = _flat_ptr(absmax32)
-        if an == 0 or bn == 0:
-            raise ZeroDivisionError("integer division or modulo by zero (empty absmax)")
-        rc = L.nf4_dequant_ref_cpu(qp, qn, ap, an, bp, bn, out.data_ptr(), code, m, n, threads)
+        rc = L.nf4_dequant_ref_cpu(qp, qn, *_ref_stats(absmax, absmax32, keep), out.data_ptr(), code, m, n, threads)
     else:
-        if absmax.dtype != torch.float32:
-            absmax = absmax.to(torch.float32)
-        absmax, ap, an = _flat_ptr(absmax)
-        rc = L.nf4_dequant_single_cpu(qp, qn, ap, an, out.data_ptr(), code, m, n, threads)
+        rc = L.nf4_dequant_single_cpu(qp, qn, *_operand(absmax, torch.float32, keep), out.data_ptr(), code, m, n,
+                                      threads)
     if rc:
         _lib.check(rc, "nf4 dequantize (cpu)")
 
@@ -328,21 +324,13 @@ def dequantize_nf4_many(modules: Iterable, out: Optional[Sequence[Optional[torch
             continue
         q = _as_u8_flat(qweight)
         _on_device(q.device, absmax, absmax32)
-        a1 = absmax.contiguous().view(-1)
-        a2 = absmax32.reshape(-1)
-        a2 = (a2 if a2.dtype == torch.float32 else a2.to(torch.float32)).contiguous()
-        if a1.numel() == 0 or a2.numel() == 0:
-            raise ZeroDivisionError("integer division or modulo by zero (empty absmax)")
-        keep.extend((q, a1, a2))
-        d = _lib.MatrixDesc(q.data_ptr(), q.numel(), a1.data_ptr(), a1.numel(), a2.data_ptr(), a2.numel(),
-                            out_t.data_ptr(), m, n)
+        keep.append(q)
+        d = _lib.MatrixDesc(q.data_ptr(), q.numel(), *_ref_stats(absmax, absmax32, keep), out_t.data_ptr(), m, n)
         groups.setdefault((q.device, code), []).append(d)
     L = _lib.lib()
     for (device, code), descs in groups.items():
         arr = (_lib.MatrixDesc * len(descs))(*descs)
-        with torch.cuda.device(device):
-            rc = L.nf4_dequant_ref_batched(arr, len(descs), code, _stream_ptr(device))
-        _lib.check(rc, "nf4 batched dequantize")
+        _stream_call("nf4 batched dequantize", device, L.nf4_dequant_ref_batched, arr, len(descs), code)
     # Temporaries in `keep` (value casts) were allocated on the stream the
     # launches use, so the caching allocator's stream-ordered reuse already
     # protects them; no record_stream needed (and it would break graph capture).
@@ -378,9 +366,8 @@ def dequantize_nf4_bnb(module) -> torch.Tensor:
 
 def _launch_bnb(q, qs, out, code, numel, bs) -> int:
     L = _lib.lib()
-    stream = _stream_ptr(q.device)
-    nested = getattr(qs, "state2", None) is not None and qs.absmax.dtype == torch.uint8
-    if nested:
+    stream = _raw_stream(q.device.index)
+    if _bnb_nested(qs):
         _on_device(q.device, qs.absmax, qs.state2.code, qs.state2.absmax)
         a1 = qs.absmax.contiguous().view(-1)
         code2 = qs.state2.code.to(torch.float32).contiguous()
@@ -401,16 +388,53 @@ def _launch_bnb(q, qs, out, code, numel, bs) -> int:
 _IDS_CODE = {torch.int32: _lib.IDS_I32, torch.int64: _lib.IDS_I64}
 
 
-def _host_offset(off):
-    """``quant_state.offset`` for the host entries: (tensor kept alive, host pointer)."""
+def _bnb_nested(qs) -> bool:
+    """Nested statistics or plain fp32 absmax: the one decision of every bitsandbytes-semantics entry."""
+    return getattr(qs, "state2", None) is not None and qs.absmax.dtype == torch.uint8
+
+
+def _offset_ptr(name: str, off, device, keep: list):
+    """``quant_state.offset`` as a pointer on ``device``: never a host read.  A tensor already there
+    passes as it is (a kernel reads its one float when it runs), a Python number becomes a scalar
+    on ``device``, None a null pointer (= 0).  A tensor made here goes to ``keep``."""
     if off is None:
-        return None, None
+        return None
+    made = off
     if not torch.is_tensor(off):
-        off = torch.tensor(float(off), dtype=torch.float32)
-    off = off.to(device="cpu", dtype=torch.float32).contiguous()
-    if off.numel() != 1:
-        raise RuntimeError(f"nf4_embedding_bnb: quant_state.offset has {off.numel()} elements, expected 1")
-    return off, off.data_ptr()
+        made = torch.tensor(float(off), dtype=torch.float32, device=device)
+    elif off.device != device or off.dtype != torch.float32:
+        made = off.to(device=device, dtype=torch.float32)  # stream-ordered copy, no synchronisation
+    if made.numel() != 1:
+        raise RuntimeError(f"{name}: quant_state.offset has {made.numel()} elements, expected 1")
+    if made is not off:
+        keep.append(made)
+    return made.data_ptr()
+
+
+def _bnb_stats(name: str, qs, dev, keep: list) -> tuple:
+    """The statistics operands of one weight in bitsandbytes semantics, in the order of the entries'
+    arguments and of ``GemmBnbMat``'s fields: ``(ap, an, cp, bp, bn, op, bs, bs2)``.  Plain fp32
+    absmax fills the nested-only fields with null and 0 and passes absmax as (bp, bn).  The pointers
+    are on ``dev``, the packed weight's device (the host for ``nf4_embedding_bnb`` under
+    NF4_BACKEND=cpu); every cast or copy made goes to ``keep``."""
+    bs = int(qs.blocksize)
+    if not _bnb_nested(qs):
+        _on_device(dev, qs.absmax)
+        return (None, 0, None, *_operand(qs.absmax, torch.float32, keep), None, bs, 0)
+    st2 = qs.state2
+    _on_device(dev, qs.absmax, st2.code, st2.absmax)
+    ap, an = _operand(qs.absmax, None, keep)
+    cp, cn = _operand(st2.code, torch.float32, keep)
+    bp, bn = _operand(st2.absmax, torch.float32, keep)
+    if cn != 256:
+        raise RuntimeError(f"{name}: state2.code has {cn} entries, expected 256")
+    return ap, an, cp, bp, bn, _offset_ptr(name, qs.offset, dev, keep), bs, int(st2.blocksize)
+
+
+def _bnb_mat(name: str, mod, dev, y_ptr, keep: list) -> "_lib.GemmBnbMat":
+    """The ``GemmBnbMat`` descriptor of one ``Linear4bit`` for the grouped and the SwiGLU launch."""
+    return _lib.GemmBnbMat(*_operand(mod.weight.data, None, keep), *_bnb_stats(name, mod.weight.quant_state, dev, keep),
+                           y_ptr, int(mod.out_features))
 
 
 def nf4_embedding_bnb(ids: torch.Tensor, module, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -447,7 +471,7 @@ def nf4_embedding_bnb(ids: torch.Tensor, module, out: Optional[torch.Tensor] = N
     bs = int(qs.blocksize)
     if bs < 64 or bs > 4096 or bs & (bs - 1):
         raise ValueError(f"nf4_embedding_bnb: blocksize {bs} is not a power of two in 64..4096")
-    nested = getattr(qs, "state2", None) is not None and qs.absmax.dtype == torch.uint8  # as _launch_bnb
+    nested = _bnb_nested(qs)
     bs2 = int(qs.state2.blocksize) if nested else 0
     if nested and (bs2 < 4 or bs2 & (bs2 - 1)):
         raise ValueError(f"nf4_embedding_bnb: state2.blocksize {bs2} is not a power of two >= 4")
@@ -473,37 +497,19 @@ def nf4_embedding_bnb(ids: torch.Tensor, module, out: Optional[torch.Tensor] = N
     count = ids.numel()
     if count == 0 or dim == 0:
         return out
+    keep = []  # every temporary outlives the call
     idc = ids.contiguous()
-    q, qp, _ = _flat_ptr(qweight)
     L = _lib.lib()
-    head = (idc.data_ptr(), _IDS_CODE[idc.dtype], count, qp)
-    if nested:
-        _on_device(dev, qs.absmax, qs.state2.code, qs.state2.absmax)
-        a1, ap, an = _flat_ptr(qs.absmax)
-        c2 = qs.state2.code
-        c2, cp, cn = _flat_ptr(c2 if c2.dtype == torch.float32 else c2.to(torch.float32))
-        a2 = qs.state2.absmax
-        a2, bp, bn = _flat_ptr(a2 if a2.dtype == torch.float32 else a2.to(torch.float32))
-        if cn != 256:
-            raise RuntimeError(f"nf4_embedding_bnb: state2.code has {cn} entries, expected 256")
-        off, op = _host_offset(qs.offset) if on_host else _offset_ptr(qs.offset, dev)
-        args = head + (ap, an, cp, bp, bn, op, bs, bs2, out.data_ptr(), code, rows, dim)
-        if on_host:
-            rc = L.nf4_embedding_bnb_cpu(*args, cpu_threads())
-        else:
-            with torch.cuda.device(dev):  # the launch's device = the weight's (not the current one)
-                rc = L.nf4_embedding_bnb(*args, _raw_stream(dev.index))
+    stats = _bnb_stats("nf4_embedding_bnb", qs, dev, keep)
+    if not nested:
+        stats = (stats[3], stats[4], bs)  # the single entries take (absmax, its count, blocksize) alone
+    args = (idc.data_ptr(), _IDS_CODE[idc.dtype], count, _operand(qweight, None, keep)[0], *stats, out.data_ptr(), code,
+            rows, dim)
+    entry = "nf4_embedding_bnb" if nested else "nf4_embedding_bnb_single"
+    if on_host:
+        _lib.check(getattr(L, entry + "_cpu")(*args, cpu_threads()), "nf4 embedding")
     else:
-        _on_device(dev, qs.absmax)
-        am = qs.absmax
-        am, ap, an = _flat_ptr(am if am.dtype == torch.float32 else am.to(torch.float32))
-        args = head + (ap, an, bs, out.data_ptr(), code, rows, dim)
-        if on_host:
-            rc = L.nf4_embedding_bnb_single_cpu(*args, cpu_threads())
-        else:
-            with torch.cuda.device(dev):
-                rc = L.nf4_embedding_bnb_single(*args, _raw_stream(dev.index))
-    _lib.check(rc, "nf4 embedding")
+        _stream_call("nf4 embedding", dev, getattr(L, entry), *args)
     return out
 
 
@@ -519,8 +525,18 @@ def _same_device(x: torch.Tensor, w: torch.Tensor) -> None:
     # what `x @ W.t()` raises for tensors on different devices (never hand a host
     # or foreign-device pointer to the kernel)
     if x.device != w.device:
-        raise RuntimeError(f"Expected all tensors to be on the same device, but found at least two devices, "
-                           f"{w.device} and {x.device}!")
+        raise _two_devices(w.device, x.device)
+
+
+def _workspace(cache: dict, device: torch.device, nbytes: int, floor: int) -> torch.Tensor:
+    """Zero-filled workspace of ``cache``, one per (device, stream), grown on demand (``floor``: the
+    smallest allocation)."""
+    key = (device.index, _raw_stream(device.index))
+    ent = cache.get(key)
+    if ent is None or ent[0].numel() < nbytes:
+        ent = cache[key] = (torch.zeros(max(nbytes, floor), dtype=torch.uint8, device=device),
+                            torch.cuda.current_stream(device))
+    return ent[0]
 
 
 def _gemm_workspace(device: torch.device, nbytes: int) -> torch.Tensor:
@@ -530,14 +546,7 @@ def _gemm_workspace(device: torch.device, nbytes: int) -> torch.Tensor:
     buffer stays valid; a new stream gets its own (calls on different streams
     may run concurrently and must not share counters).
     """
-    stream = torch.cuda.current_stream(device)
-    key = (device.index, stream.cuda_stream)
-    ent = _GEMM_WS.get(key)
-    ws = ent[0] if ent is not None else None
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.zeros(max(nbytes, 1 << 16), dtype=torch.uint8, device=device)
-        _GEMM_WS[key] = (ws, stream)
-    return ws
+    return _workspace(_GEMM_WS, device, nbytes, 1 << 16)
 
 
 # nf4_moe_down_bnb's workspaces, apart from the shared ones: the launch leaves its 16-bit products
@@ -551,12 +560,55 @@ _MOE_DOWN_WS = {}
 
 def _moe_down_workspace(device: torch.device, nbytes: int) -> torch.Tensor:
     """``_gemm_workspace`` for ``nf4_moe_down_bnb`` alone: one per (device, stream), grown on demand."""
-    stream = torch.cuda.current_stream(device)
-    key = (device.index, stream.cuda_stream)
-    ent = _MOE_DOWN_WS.get(key)
-    if ent is None or ent[0].numel() < nbytes:
-        ent = _MOE_DOWN_WS[key] = (torch.zeros(nbytes, dtype=torch.uint8, device=device), stream)
-    return ent[0]
+    return _workspace(_MOE_DOWN_WS, device, nbytes, 0)
+
+
+def _stream_call(what: str, dev, entry, *args) -> None:
+    """One entry on the current stream of ``dev``, the tensors' device (not the current one): the stream
+    handle is the entry's last argument, a failure raises as ``what``."""
+    with torch.cuda.device(dev):
+        rc = entry(*args, _raw_stream(dev.index))
+    _lib.check(rc, what)
+
+
+def _fused_call(what: str, dev, entry, args, size, size_args, workspace=_gemm_workspace, cfg=(None,)) -> None:
+    """The one launch of a fused route, on ``dev``: ask ``size(*size_args)`` for the workspace bytes, take
+    the current stream's workspace (null when the entry wants none), and call ``entry`` with ``args``,
+    then the workspace, its size, the plan override ``cfg`` (none; ``()`` for an entry without the
+    argument) and the current stream's handle.  Whatever ``args`` points to is the caller's to hold."""
+    with torch.cuda.device(dev):
+        ws_bytes = size(*size_args)
+        wp = workspace(dev, ws_bytes).data_ptr() if ws_bytes else None
+        rc = entry(*args, wp, ws_bytes, *cfg, _raw_stream(dev.index))
+    _lib.check(rc, what)
+
+
+def _lead_rows(x: torch.Tensor, K: int) -> tuple:
+    """x's leading dims and its row count as a ``[M, K]`` matrix."""
+    return x.shape[:-1], (x.numel() // K if K else 0)
+
+
+def _rows(x: torch.Tensor, K: int, dtype: torch.dtype, align16: bool) -> torch.Tensor:
+    """x as an entry reads it: ``[M, K]``, ``dtype``, contiguous and, for the entries that load 16 bytes
+    at a time (``align16``), 16-byte aligned -- a view at an odd offset is cloned."""
+    xc = x.reshape(-1, K)
+    if xc.dtype != dtype:
+        xc = xc.to(dtype)
+    xc = xc.contiguous()
+    if align16 and xc.data_ptr() % 16:
+        xc = xc.clone()
+    return xc
+
+
+def _check_out(name: str, out: Optional[torch.Tensor], shape: list, dtype: torch.dtype, dev) -> None:
+    if out is not None and (list(out.shape) != shape or out.dtype != dtype or out.device != dev
+                            or not out.is_contiguous()):
+        raise ValueError(f"{name}: out must be a contiguous {dtype} {shape} tensor on {dev}")
+
+
+def _into(out: Optional[torch.Tensor], value: torch.Tensor) -> torch.Tensor:
+    """``value``, copied into ``out`` when the caller gave one."""
+    return value if out is None else out.copy_(value)
 
 
 def release_gemm_workspaces() -> None:
@@ -612,8 +664,7 @@ def nf4_linear(x: torch.Tensor, module, bias: Optional[torch.Tensor] = None) -> 
     N, K = m, n
     if x.shape[-1] != K:
         raise RuntimeError(f"nf4_linear: x has {x.shape[-1]} features, weight expects {K}")
-    lead = x.shape[:-1]
-    M = x.numel() // K if K else 0
+    lead, M = _lead_rows(x, K)
     fused = (qweight.device.type == "cuda" and dtype in (torch.float16, torch.bfloat16)
              and absmax.dtype == torch.uint8 and 0 < M <= _lib.GEMM_MAX_M
              and N % 64 == 0 and K % 128 == 0 and qweight.numel() * qweight.element_size() == N * K // 2
@@ -622,45 +673,19 @@ def nf4_linear(x: torch.Tensor, module, bias: Optional[torch.Tensor] = None) -> 
         w = triton_dequantize_nf4(module)
         y = x.to(dtype) @ w.t()
     else:
-        xc = x.reshape(M, K)
-        if xc.dtype != dtype:
-            xc = xc.to(dtype)
-        xc = xc.contiguous()
-        y = torch.empty((M, N), dtype=dtype, device=qweight.device)
-        _on_device(qweight.device, absmax, absmax32)
+        dev = qweight.device
+        xc = _rows(x, K, dtype, False)
+        y = torch.empty((M, N), dtype=dtype, device=dev)
+        _on_device(dev, absmax, absmax32)
         L = _lib.lib()
-        ws_bytes = L.nf4_gemm_workspace_bytes(M, N, K)
-        with torch.cuda.device(qweight.device):
-            ws = _gemm_workspace(qweight.device, ws_bytes) if ws_bytes else None
-            q, qp, qn = _flat_ptr(qweight)
-            a1, ap, an = _flat_ptr(absmax)
-            a2 = absmax32 if absmax32.dtype == torch.float32 else absmax32.to(torch.float32)
-            a2, bp, bn = _flat_ptr(a2)
-            if an == 0 or bn == 0:
-                raise ZeroDivisionError("integer division or modulo by zero (empty absmax)")
-            rc = L.nf4_gemm_ref(xc.data_ptr(), M, qp, qn, ap, an, bp, bn, y.data_ptr(), _dtype_code(dtype), N, K,
-                                ws.data_ptr() if ws is not None else None, ws_bytes,
-                                torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "nf4 fused gemm")
+        keep = []
+        args = (xc.data_ptr(), M, *_operand(qweight, None, keep), *_ref_stats(absmax, absmax32, keep), y.data_ptr(),
+                _dtype_code(dtype), N, K)
+        _fused_call("nf4 fused gemm", dev, L.nf4_gemm_ref, args, L.nf4_gemm_workspace_bytes, (M, N, K), cfg=())
         y = y.reshape(*lead, N)
     if bias is not None:
         y = y + bias.to(y.dtype)
     return y.reshape(*lead, N)
-
-
-def _offset_ptr(off, device):
-    """``quant_state.offset`` as (tensor kept alive, device pointer): never a host read.
-    A device tensor passes as it is (the kernel reads its one float when it runs), a Python
-    number becomes a device scalar, None a null pointer (= 0)."""
-    if off is None:
-        return None, None
-    if not torch.is_tensor(off):
-        off = torch.tensor(float(off), dtype=torch.float32, device=device)
-    if off.device != device or off.dtype != torch.float32:
-        off = off.to(device=device, dtype=torch.float32)  # stream-ordered copy, no synchronisation
-    if off.numel() != 1:
-        raise RuntimeError(f"nf4_linear_bnb: quant_state.offset has {off.numel()} elements, expected 1")
-    return off, off.data_ptr()
 
 
 # Rows up to which nf4_linear_bnb routes to the row-tiled entry (nf4_gemm_bnb_mt*): the largest
@@ -679,7 +704,7 @@ def _bnb_gemm_blocksizes(qs) -> bool:
     bs = int(qs.blocksize)
     if bs < 64 or bs > 4096 or bs & (bs - 1):
         return False
-    if getattr(qs, "state2", None) is not None and qs.absmax.dtype == torch.uint8:
+    if _bnb_nested(qs):
         bs2 = int(qs.state2.blocksize)
         return bs2 >= 4 and not bs2 & (bs2 - 1)
     return True
@@ -715,8 +740,7 @@ def nf4_linear_bnb(x: torch.Tensor, module, bias: Optional[torch.Tensor] = None)
         _same_device(x, qweight)
     if x.shape[-1] != K:
         raise RuntimeError(f"nf4_linear_bnb: x has {x.shape[-1]} features, weight expects {K}")
-    lead = x.shape[:-1]
-    M = x.numel() // K if K else 0
+    lead, M = _lead_rows(x, K)
     fused = (qweight.device.type == "cuda" and dtype in (torch.float16, torch.bfloat16)
              and 0 < M <= GEMM_MT_ROUTED_M and N % 64 == 0 and K % 128 == 0
              and qweight.dtype == torch.uint8 and qweight.numel() == N * K // 2
@@ -731,43 +755,18 @@ def nf4_linear_bnb(x: torch.Tensor, module, bias: Optional[torch.Tensor] = None)
         y = x.to(w.dtype) @ w.t()
     else:
         dev = qweight.device
-        xc = x.reshape(M, K)
-        if xc.dtype != dtype:
-            xc = xc.to(dtype)
-        xc = xc.contiguous()
-        if mt and xc.data_ptr() % 16:
-            xc = xc.clone()  # a view at an odd offset: the row-tiled entry loads 16 bytes at a time
+        xc = _rows(x, K, dtype, mt)  # the row-tiled entry alone loads 16 bytes at a time
         y = torch.empty((M, N), dtype=dtype, device=dev)
         L = _lib.lib()
-        bs = int(qs.blocksize)
-        nested = getattr(qs, "state2", None) is not None and qs.absmax.dtype == torch.uint8  # as _launch_bnb
-        with torch.cuda.device(dev):
-            ws_bytes = (L.nf4_gemm_bnb_mt_workspace_bytes if mt else L.nf4_gemm_bnb_workspace_bytes)(M, N, K, None)
-            ws = _gemm_workspace(dev, ws_bytes) if ws_bytes else None
-            wp = ws.data_ptr() if ws is not None else None
-            q, qp, qn = _flat_ptr(qweight)
-            stream = torch.cuda.current_stream().cuda_stream
-            gemm_nested = L.nf4_gemm_bnb_mt if mt else L.nf4_gemm_bnb
-            gemm_single = L.nf4_gemm_bnb_mt_single if mt else L.nf4_gemm_bnb_single
-            if nested:
-                _on_device(dev, qs.absmax, qs.state2.code, qs.state2.absmax)
-                a1, ap, an = _flat_ptr(qs.absmax)
-                c2 = qs.state2.code
-                c2, cp, cn = _flat_ptr(c2 if c2.dtype == torch.float32 else c2.to(torch.float32))
-                a2 = qs.state2.absmax
-                a2, bp, bn = _flat_ptr(a2 if a2.dtype == torch.float32 else a2.to(torch.float32))
-                if cn != 256:
-                    raise RuntimeError(f"nf4_linear_bnb: state2.code has {cn} entries, expected 256")
-                off, op = _offset_ptr(qs.offset, dev)
-                rc = gemm_nested(xc.data_ptr(), M, qp, qn, ap, an, cp, bp, bn, op, bs, int(qs.state2.blocksize),
-                                 y.data_ptr(), _dtype_code(dtype), N, K, wp, ws_bytes, None, stream)
-            else:
-                _on_device(dev, qs.absmax)
-                am = qs.absmax
-                am, ap, an = _flat_ptr(am if am.dtype == torch.float32 else am.to(torch.float32))
-                rc = gemm_single(xc.data_ptr(), M, qp, qn, ap, an, bs, y.data_ptr(), _dtype_code(dtype),
-                                 N, K, wp, ws_bytes, None, stream)
-        _lib.check(rc, "nf4 fused bnb gemm")
+        keep = []
+        entry = "nf4_gemm_bnb_mt" if mt else "nf4_gemm_bnb"
+        stats = _bnb_stats("nf4_linear_bnb", qs, dev, keep)
+        if not _bnb_nested(qs):
+            entry += "_single"
+            stats = (stats[3], stats[4], stats[6])  # the single entries take (absmax, its count, blocksize) alone
+        args = (xc.data_ptr(), M, *_operand(qweight, None, keep), *stats, y.data_ptr(), _dtype_code(dtype), N, K)
+        _fused_call("nf4 fused bnb gemm", dev, getattr(L, entry), args,
+                    L.nf4_gemm_bnb_mt_workspace_bytes if mt else L.nf4_gemm_bnb_workspace_bytes, (M, N, K, None))
         y = y.reshape(*lead, N)
     if bias is not None:
         y = y + bias.to(y.dtype)
@@ -792,8 +791,7 @@ def nf4_linear_grouped(x: torch.Tensor, modules: Sequence, biases: Optional[Sequ
         return []
     preps = [_prepare(mod) for mod in modules]
     K = x.shape[-1]
-    lead = x.shape[:-1]
-    M = x.numel() // K if K else 0
+    lead, M = _lead_rows(x, K)
     dtype = preps[0][3]
     dev = preps[0][0].device
     grouped = 1 < len(modules) <= _lib.GEMM_GROUP_MAX and 0 < M <= _lib.GEMM_MAX_M and K % 128 == 0
@@ -805,45 +803,26 @@ def nf4_linear_grouped(x: torch.Tensor, modules: Sequence, biases: Optional[Sequ
         return [nf4_linear(x, mod, bias=b) for mod, b in zip(modules, biases)]
     _require_device(preps[0][0])
     _same_device(x, preps[0][0])
-    xc = x.reshape(M, K)
-    if xc.dtype != dtype:
-        xc = xc.to(dtype)
-    xc = xc.contiguous()
+    xc = _rows(x, K, dtype, False)
+    # keep: the contiguous copies (when q / a1 / a2 are strided views) must outlive the launch -- the
+    # caching allocator would hand their blocks to the next torch.empty
     ys, keep = [], []
     mats = (_lib.GemmMat * len(modules))()
     for i, (q, a1, a2, _dt, m, _n) in enumerate(preps):
         _on_device(dev, a1, a2)
         y = torch.empty((M, m), dtype=dtype, device=dev)
-        # the contiguous copies (when q / a1 / a2 are strided views) must outlive the
-        # launch: the caching allocator would hand their blocks to the next torch.empty
-        qc, qp, qn = _flat_ptr(q)
-        a1c, ap, an = _flat_ptr(a1)
-        a2f = a2 if a2.dtype == torch.float32 else a2.to(torch.float32)
-        a2f, bp, bn = _flat_ptr(a2f)
-        if an == 0 or bn == 0:
-            raise ZeroDivisionError("integer division or modulo by zero (empty absmax)")
-        keep.extend((qc, a1c, a2f))
-        mats[i] = _lib.GemmMat(qp, qn, ap, an, bp, bn, y.data_ptr(), m)
+        mats[i] = _lib.GemmMat(*_operand(q, None, keep), *_ref_stats(a1, a2, keep), y.data_ptr(), m)
         ys.append(y)
     L = _lib.lib()
-    with torch.cuda.device(dev):
-        ws_bytes = L.nf4_gemm_grouped_workspace_bytes(M, K, mats, len(modules), None)
-        ws = _gemm_workspace(dev, ws_bytes) if ws_bytes else None
-        rc = L.nf4_gemm_ref_grouped(xc.data_ptr(), M, K, mats, len(modules), _dtype_code(dtype),
-                                    ws.data_ptr() if ws is not None else None, ws_bytes, None,
-                                    torch.cuda.current_stream().cuda_stream)
-    _lib.check(rc, "nf4 fused grouped gemm")
+    _fused_call("nf4 fused grouped gemm", dev, L.nf4_gemm_ref_grouped,
+                (xc.data_ptr(), M, K, mats, len(modules), _dtype_code(dtype)),
+                L.nf4_gemm_grouped_workspace_bytes, (M, K, mats, len(modules), None))
     out = []
     for y, b, (_q, _a1, _a2, _dt, m, _n) in zip(ys, biases, preps):
         if b is not None:
             y = y + b.to(y.dtype)
         out.append(y.reshape(*lead, m))
     return out
-
-
-def _bnb_nested(qs) -> bool:
-    """Nested statistics or plain fp32 absmax, decided as ``_launch_bnb`` and ``nf4_linear_bnb`` do."""
-    return getattr(qs, "state2", None) is not None and qs.absmax.dtype == torch.uint8
 
 
 def nf4_linear_bnb_grouped(x: torch.Tensor, modules: Sequence,
@@ -886,47 +865,18 @@ def nf4_linear_bnb_grouped(x: torch.Tensor, modules: Sequence,
                    and _bnb_nested(qs) == nested)
     if not grouped:
         return [nf4_linear_bnb(x, mod, b) for mod, b in zip(modules, biases)]
-    xc = x.reshape(M, K)
-    if xc.dtype != dtype:
-        xc = xc.to(dtype)
-    xc = xc.contiguous()
+    xc = _rows(x, K, dtype, False)
     ys, keep = [], []  # keep: every temporary outlives the enqueue (the caching allocator reuses freed blocks)
     mats = (_lib.GemmBnbMat * len(modules))()
-    with torch.cuda.device(dev):
-        for i, mod in enumerate(modules):
-            q, qs, N = mod.weight.data, mod.weight.quant_state, int(mod.out_features)
-            y = torch.empty((M, N), dtype=dtype, device=dev)
-            qc, qp, qn = _flat_ptr(q)
-            if nested:
-                _on_device(dev, qs.absmax, qs.state2.code, qs.state2.absmax)
-                a1, ap, an = _flat_ptr(qs.absmax)
-                c2 = qs.state2.code
-                c2, cp, cn = _flat_ptr(c2 if c2.dtype == torch.float32 else c2.to(torch.float32))
-                a2 = qs.state2.absmax
-                a2, bp, bn = _flat_ptr(a2 if a2.dtype == torch.float32 else a2.to(torch.float32))
-                if cn != 256:
-                    raise RuntimeError(f"nf4_linear_bnb_grouped: state2.code has {cn} entries, expected 256")
-                off, op = _offset_ptr(qs.offset, dev)
-                keep.extend((qc, a1, c2, a2, off))
-                mats[i] = _lib.GemmBnbMat(qp, qn, ap, an, cp, bp, bn, op, int(qs.blocksize),
-                                          int(qs.state2.blocksize), y.data_ptr(), N)
-            else:
-                _on_device(dev, qs.absmax)
-                am = qs.absmax
-                am, ap, an = _flat_ptr(am if am.dtype == torch.float32 else am.to(torch.float32))
-                keep.extend((qc, am))
-                mats[i] = _lib.GemmBnbMat(qp, qn, None, 0, None, ap, an, None, int(qs.blocksize), 0,
-                                          y.data_ptr(), N)
-            ys.append(y)
-        L = _lib.lib()
-        mp = ctypes.cast(mats, ctypes.c_void_p)
-        single = 0 if nested else 1
-        ws_bytes = L.nf4_gemm_bnb_grouped_workspace_bytes(M, K, mp, len(modules), single, None)
-        ws = _gemm_workspace(dev, ws_bytes) if ws_bytes else None
-        rc = L.nf4_gemm_bnb_grouped(xc.data_ptr(), M, K, mp, len(modules), single, _dtype_code(dtype),
-                                    ws.data_ptr() if ws is not None else None, ws_bytes, None,
-                                    torch.cuda.current_stream().cuda_stream)
-    _lib.check(rc, "nf4 fused grouped bnb gemm")
+    for i, mod in enumerate(modules):
+        ys.append(torch.empty((M, int(mod.out_features)), dtype=dtype, device=dev))
+        mats[i] = _bnb_mat("nf4_linear_bnb_grouped", mod, dev, ys[i].data_ptr(), keep)
+    L = _lib.lib()
+    mp = ctypes.cast(mats, ctypes.c_void_p)
+    single = 0 if nested else 1
+    _fused_call("nf4 fused grouped bnb gemm", dev, L.nf4_gemm_bnb_grouped,
+                (xc.data_ptr(), M, K, mp, len(modules), single, _dtype_code(dtype)),
+                L.nf4_gemm_bnb_grouped_workspace_bytes, (M, K, mp, len(modules), single, None))
     del keep
     out = []
     for y, b, mod in zip(ys, biases, modules):
@@ -967,8 +917,7 @@ def _moe_args(name: str, x: torch.Tensor, experts, expert_ids: torch.Tensor):
     else:
         raise RuntimeError(f"{name}: x must be [{T}, {K}] or [{T}, {k}, {K}], got {tuple(x.shape)}")
     if x.device != dev or expert_ids.device != dev:
-        raise RuntimeError(f"Expected all tensors to be on the same device, but found at least two devices, "
-                           f"{dev} and {x.device if x.device != dev else expert_ids.device}!")
+        raise _two_devices(dev, x.device if x.device != dev else expert_ids.device)
     return T, k, x_div, x3
 
 
@@ -986,12 +935,8 @@ def _moe_fusable(x: torch.Tensor, experts, P: int, max_pairs: int = _lib.MOE_MAX
 
 def _moe_operands(x: torch.Tensor, expert_ids: torch.Tensor, dtype: torch.dtype):
     """x and the ids as the expert entries read them: the dtype, contiguous, x 16-byte aligned, int32 ids."""
-    xc = x if x.dtype == dtype else x.to(dtype)
-    xc = xc.contiguous()
-    if xc.data_ptr() % 16:
-        xc = xc.clone()  # a view at an odd offset: the entry loads 16 bytes at a time
     ids = expert_ids if expert_ids.dtype == torch.int32 else expert_ids.to(torch.int32)
-    return xc, ids.contiguous()
+    return _rows(x, x.shape[-1], dtype, True), ids.contiguous()
 
 
 def _moe_desc(experts) -> "_lib.MoeExperts":
@@ -1051,10 +996,9 @@ def nf4_moe_linear_bnb(x: torch.Tensor, experts, expert_ids: torch.Tensor,
     dtype = experts.dtype
     dev = experts.weight.data.device
     T, k, x_div, x3 = _moe_args("nf4_moe_linear_bnb", x, experts, expert_ids)
+    _check_out("nf4_moe_linear_bnb", out, [T, k, N], dtype, dev)
     if out is None:
         out = torch.empty((T, k, N), dtype=dtype, device=dev)
-    elif tuple(out.shape) != (T, k, N) or out.dtype != dtype or out.device != dev or not out.is_contiguous():
-        raise ValueError(f"nf4_moe_linear_bnb: out must be a contiguous {dtype} [{T}, {k}, {N}] tensor on {dev}")
     P = T * k
     if P == 0:
         return out
@@ -1067,13 +1011,8 @@ def nf4_moe_linear_bnb(x: torch.Tensor, experts, expert_ids: torch.Tensor,
     size, entry = ((L.nf4_gemm_bnb_moe_rb_workspace_bytes, L.nf4_gemm_bnb_moe_rb) if row_blocks
                    else (L.nf4_gemm_bnb_moe_workspace_bytes, L.nf4_gemm_bnb_moe))
     dp = ctypes.cast(ctypes.pointer(desc), ctypes.c_void_p)
-    with torch.cuda.device(dev):
-        ws_bytes = size(P, dp, None)
-        ws = _gemm_workspace(dev, ws_bytes) if ws_bytes else None
-        rc = entry(xc.data_ptr(), ids.data_ptr(), P, x_div, dp, out.data_ptr(), _dtype_code(dtype),
-                   ws.data_ptr() if ws is not None else None, ws_bytes, None,
-                   torch.cuda.current_stream().cuda_stream)
-    _lib.check(rc, "nf4 fused moe gemm")
+    _fused_call("nf4 fused moe gemm", dev, entry,
+                (xc.data_ptr(), ids.data_ptr(), P, x_div, dp, out.data_ptr(), _dtype_code(dtype)), size, (P, dp, None))
     return out
 
 
@@ -1136,61 +1075,24 @@ def nf4_swiglu_bnb(x: torch.Tensor, gate_proj, up_proj, out: Optional[torch.Tens
                            f"[{int(up_proj.out_features)}, {int(up_proj.in_features)}]")
     if x.shape[-1] != K:
         raise RuntimeError(f"nf4_swiglu_bnb: x has {x.shape[-1]} features, the weights expect {K}")
-    lead = x.shape[:-1]
-    M = x.numel() // K if K else 0
+    lead, M = _lead_rows(x, K)
     dtype = gate_proj.weight.quant_state.dtype
     dev = gate_proj.weight.data.device
-    if out is not None and (tuple(out.shape) != (*lead, I) or out.dtype != dtype or out.device != x.device
-                            or not out.is_contiguous()):
-        raise ValueError(f"nf4_swiglu_bnb: out must be a contiguous {dtype} {[*lead, I]} tensor on {x.device}")
+    _check_out("nf4_swiglu_bnb", out, [*lead, I], dtype, x.device)
     if not _swiglu_fused(x, gate_proj, up_proj, M, I, K):
         g, u = nf4_linear_bnb_grouped(x, [gate_proj, up_proj],
                                       [getattr(gate_proj, "bias", None), getattr(up_proj, "bias", None)])
-        h = torch.nn.functional.silu(g) * u
-        if out is None:
-            return h
-        out.copy_(h)
-        return out
-    xc = x.reshape(M, K)
-    if xc.dtype != dtype:
-        xc = xc.to(dtype)
-    xc = xc.contiguous()
-    if xc.data_ptr() % 16:
-        xc = xc.clone()  # a view at an odd offset: the entry loads 16 bytes at a time
+        return _into(out, torch.nn.functional.silu(g) * u)
+    xc = _rows(x, K, dtype, True)
     h = out if out is not None else torch.empty((*lead, I), dtype=dtype, device=dev)
-    nested = _bnb_nested(gate_proj.weight.quant_state)
     keep = []  # every temporary outlives the enqueue (the caching allocator reuses freed blocks)
-    mats = (_lib.GemmBnbMat * 2)()
-    with torch.cuda.device(dev):
-        for i, mod in enumerate((gate_proj, up_proj)):  # the descriptors of nf4_linear_bnb_grouped
-            q, qs = mod.weight.data, mod.weight.quant_state
-            qc, qp, qn = _flat_ptr(q)
-            if nested:
-                _on_device(dev, qs.absmax, qs.state2.code, qs.state2.absmax)
-                a1, ap, an = _flat_ptr(qs.absmax)
-                c2 = qs.state2.code
-                c2, cp, cn = _flat_ptr(c2 if c2.dtype == torch.float32 else c2.to(torch.float32))
-                a2 = qs.state2.absmax
-                a2, bp, bn = _flat_ptr(a2 if a2.dtype == torch.float32 else a2.to(torch.float32))
-                if cn != 256:
-                    raise RuntimeError(f"nf4_swiglu_bnb: state2.code has {cn} entries, expected 256")
-                off, op = _offset_ptr(qs.offset, dev)
-                keep.extend((qc, a1, c2, a2, off))
-                mats[i] = _lib.GemmBnbMat(qp, qn, ap, an, cp, bp, bn, op, 64, int(qs.state2.blocksize), None, I)
-            else:
-                _on_device(dev, qs.absmax)
-                am = qs.absmax
-                am, ap, an = _flat_ptr(am if am.dtype == torch.float32 else am.to(torch.float32))
-                keep.extend((qc, am))
-                mats[i] = _lib.GemmBnbMat(qp, qn, None, 0, None, ap, an, None, 64, 0, None, I)
-        L = _lib.lib()
-        ws_bytes = L.nf4_gemm_bnb_mt_swiglu_workspace_bytes(M, I, K, None)
-        ws = _gemm_workspace(dev, ws_bytes) if ws_bytes else None
-        rc = L.nf4_gemm_bnb_mt_swiglu(xc.data_ptr(), M, K, ctypes.cast(mats, ctypes.c_void_p), 0 if nested else 1,
-                                      _lib.ACT_SILU, h.data_ptr(), _dtype_code(dtype),
-                                      ws.data_ptr() if ws is not None else None, ws_bytes, None,
-                                      torch.cuda.current_stream().cuda_stream)
-    _lib.check(rc, "nf4 fused swiglu gemm")
+    # the descriptors of nf4_linear_bnb_grouped, without an output of their own
+    mats = (_lib.GemmBnbMat * 2)(*[_bnb_mat("nf4_swiglu_bnb", mod, dev, None, keep) for mod in (gate_proj, up_proj)])
+    L = _lib.lib()
+    _fused_call("nf4 fused swiglu gemm", dev, L.nf4_gemm_bnb_mt_swiglu,
+                (xc.data_ptr(), M, K, ctypes.cast(mats, ctypes.c_void_p),
+                 0 if _bnb_nested(gate_proj.weight.quant_state) else 1, _lib.ACT_SILU, h.data_ptr(), _dtype_code(dtype)),
+                L.nf4_gemm_bnb_mt_swiglu_workspace_bytes, (M, I, K, None))
     del keep
     return h
 
@@ -1250,34 +1152,23 @@ def nf4_moe_swiglu_bnb(x: torch.Tensor, gate_experts, up_experts, expert_ids: to
     dev = gate_experts.weight.data.device
     T, k, x_div, _ = _moe_args("nf4_moe_swiglu_bnb", x, gate_experts, expert_ids)
     if up_experts.weight.data.device != dev:
-        raise RuntimeError(f"Expected all tensors to be on the same device, but found at least two devices, "
-                           f"{dev} and {up_experts.weight.data.device}!")
-    if out is not None and (tuple(out.shape) != (T, k, I) or out.dtype != dtype or out.device != dev
-                            or not out.is_contiguous()):
-        raise ValueError(f"nf4_moe_swiglu_bnb: out must be a contiguous {dtype} [{T}, {k}, {I}] tensor on {dev}")
+        raise _two_devices(dev, up_experts.weight.data.device)
+    _check_out("nf4_moe_swiglu_bnb", out, [T, k, I], dtype, dev)
     P = T * k
     fused = (MOE_SWIGLU_ROUTED_MIN_P <= P <= MOE_SWIGLU_ROUTED_MAX_P and _moe_fusable(x, gate_experts, P)
              and _moe_fusable(x, up_experts, P))
     if not fused:
-        h = torch.nn.functional.silu(nf4_moe_linear_bnb(x, gate_experts, expert_ids)) \
-            * nf4_moe_linear_bnb(x, up_experts, expert_ids)
-        if out is None:
-            return h
-        out.copy_(h)
-        return out
+        return _into(out, torch.nn.functional.silu(nf4_moe_linear_bnb(x, gate_experts, expert_ids))
+                     * nf4_moe_linear_bnb(x, up_experts, expert_ids))
     if out is None:
         out = torch.empty((T, k, I), dtype=dtype, device=dev)
     xc, ids = _moe_operands(x, expert_ids, dtype)
     descs = (_lib.MoeExperts * 2)(_moe_desc(gate_experts), _moe_desc(up_experts))
     L = _lib.lib()
     dp = ctypes.cast(descs, ctypes.c_void_p)
-    with torch.cuda.device(dev):
-        ws_bytes = L.nf4_gemm_bnb_moe_swiglu_workspace_bytes(P, dp, None)
-        ws = _gemm_workspace(dev, ws_bytes) if ws_bytes else None
-        rc = L.nf4_gemm_bnb_moe_swiglu(xc.data_ptr(), ids.data_ptr(), P, x_div, dp, _lib.ACT_SILU, out.data_ptr(),
-                                       _dtype_code(dtype), ws.data_ptr() if ws is not None else None, ws_bytes, None,
-                                       torch.cuda.current_stream().cuda_stream)
-    _lib.check(rc, "nf4 fused moe swiglu gemm")
+    _fused_call("nf4 fused moe swiglu gemm", dev, L.nf4_gemm_bnb_moe_swiglu,
+                (xc.data_ptr(), ids.data_ptr(), P, x_div, dp, _lib.ACT_SILU, out.data_ptr(), _dtype_code(dtype)),
+                L.nf4_gemm_bnb_moe_swiglu_workspace_bytes, (P, dp, None))
     return out
 
 
@@ -1353,11 +1244,8 @@ def nf4_moe_down_bnb(h: torch.Tensor, experts, expert_ids: torch.Tensor, routing
         raise ValueError(f"nf4_moe_down_bnb: routing_weights must be a float [{T}, {k}] tensor, got "
                          f"{routing_weights.dtype} {tuple(routing_weights.shape)}")
     if routing_weights.device != dev:
-        raise RuntimeError(f"Expected all tensors to be on the same device, but found at least two devices, "
-                           f"{dev} and {routing_weights.device}!")
-    if out is not None and (tuple(out.shape) != (T, N) or out.dtype != dtype or out.device != dev
-                            or not out.is_contiguous()):
-        raise ValueError(f"nf4_moe_down_bnb: out must be a contiguous {dtype} [{T}, {N}] tensor on {dev}")
+        raise _two_devices(dev, routing_weights.device)
+    _check_out("nf4_moe_down_bnb", out, [T, N], dtype, dev)
     P = T * k
     fused = (MOE_DOWN_ROUTED_MIN_P <= P <= MOE_DOWN_ROUTED_MAX_P and _moe_fusable(h, experts, P)
              and not (torch.is_grad_enabled() and routing_weights.requires_grad))
@@ -1366,10 +1254,7 @@ def nf4_moe_down_bnb(h: torch.Tensor, experts, expert_ids: torch.Tensor, routing
             y = torch.zeros((T, N), dtype=dtype, device=dev)
         else:
             y = _moe_down_chain(nf4_moe_linear_bnb(h, experts, expert_ids), routing_weights)
-        if out is None:
-            return y
-        out.copy_(y)
-        return out
+        return _into(out, y)
     if out is None:
         out = torch.empty((T, N), dtype=dtype, device=dev)
     hc, ids = _moe_operands(h, expert_ids, dtype)
@@ -1378,14 +1263,10 @@ def nf4_moe_down_bnb(h: torch.Tensor, experts, expert_ids: torch.Tensor, routing
     desc = _moe_desc(experts)
     L = _lib.lib()
     dp = ctypes.cast(ctypes.pointer(desc), ctypes.c_void_p)
-    with torch.cuda.device(dev):
-        ws_bytes = L.nf4_gemm_bnb_moe_down_workspace_bytes(P, dp, None)
-        ws = _moe_down_workspace(dev, ws_bytes)
-        rc = L.nf4_gemm_bnb_moe_down(hc.data_ptr(), ids.data_ptr(), P, x_div, k, rw.data_ptr(),
-                                     _lib.F32 if rw.dtype == torch.float32 else _dtype_code(dtype), dp, out.data_ptr(),
-                                     _dtype_code(dtype), ws.data_ptr(), ws_bytes, None,
-                                     torch.cuda.current_stream().cuda_stream)
-    _lib.check(rc, "nf4 fused moe down gemm")
+    _fused_call("nf4 fused moe down gemm", dev, L.nf4_gemm_bnb_moe_down,
+                (hc.data_ptr(), ids.data_ptr(), P, x_div, k, rw.data_ptr(),
+                 _lib.F32 if rw.dtype == torch.float32 else _dtype_code(dtype), dp, out.data_ptr(), _dtype_code(dtype)),
+                L.nf4_gemm_bnb_moe_down_workspace_bytes, (P, dp, None), workspace=_moe_down_workspace)
     return out
 
 
@@ -1425,44 +1306,65 @@ def _lora_composite(y: torch.Tensor, x: torch.Tensor, A: torch.Tensor, B: torch.
     return y + (u * scaling).to(y.dtype)
 
 
-def _lora_fusable(x: torch.Tensor, module, A: torch.Tensor, B: torch.Tensor, M: int) -> bool:
-    """nf4_linear_lora_bnb's fused-path rules (its docstring) for one adapter."""
+def _adapter_fusable(x: torch.Tensor, module, A: torch.Tensor, B: torch.Tensor, r: int, M: int, min_m: int,
+                     max_m: int) -> bool:
+    """The fused-path rules the adapter launches share (nf4_linear_lora_bnb's docstring): ``A`` and ``B``
+    are an adapter or a stack of rank ``r``, ``min_m .. max_m`` the function's routed rows."""
     dtype = module.weight.quant_state.dtype
     dev = module.weight.data.device
     N, K = int(module.out_features), int(module.in_features)
-    if not (dev.type == "cuda" and x.device == dev and A.device == dev and B.device == dev
+    return (dev.type == "cuda" and x.device == dev and A.device == dev and B.device == dev
             and dtype in (torch.float16, torch.bfloat16) and A.dtype == dtype and B.dtype == dtype
-            and max(1, LORA_ROUTED_MIN_M) <= M <= min(LORA_ROUTED_MAX_M, _lib.LORA_MAX_M)
-            and A.dim() == 2 and B.dim() == 2):
-        return False
-    r = int(A.shape[0])
-    return (tuple(A.shape) == (r, K) and tuple(B.shape) == (N, r) and r % 8 == 0 and 8 <= r <= _lib.LORA_MAX_R
-            and K % 32 == 0 and K >= 32 and N % 16 == 0 and N >= 16
+            and max(1, min_m) <= M <= min(max_m, _lib.LORA_MAX_M)
+            and r % 8 == 0 and 8 <= r <= _lib.LORA_MAX_R and K % 32 == 0 and K >= 32 and N % 16 == 0 and N >= 16
             and A.is_contiguous() and B.is_contiguous() and A.data_ptr() % 16 == 0 and B.data_ptr() % 16 == 0
             and not (torch.is_grad_enabled() and (x.requires_grad or A.requires_grad or B.requires_grad)))
 
 
+def _lora_fusable(x: torch.Tensor, module, A: torch.Tensor, B: torch.Tensor, M: int) -> bool:
+    """nf4_linear_lora_bnb's fused-path rules (its docstring) for one adapter."""
+    if A.dim() != 2 or B.dim() != 2:
+        return False
+    r = int(A.shape[0])
+    return (tuple(A.shape) == (r, int(module.in_features)) and tuple(B.shape) == (int(module.out_features), r)
+            and _adapter_fusable(x, module, A, B, r, M, LORA_ROUTED_MIN_M, LORA_ROUTED_MAX_M))
+
+
 def _lora_add(x: torch.Tensor, M: int, K: int, dtype: torch.dtype, items) -> None:
     """ONE nf4_lora_add launch: ``items`` is [(y [.., N] contiguous, updated in place, A, B, scaling)]."""
-    dev = x.device
-    xc = x.reshape(M, K)
-    if xc.dtype != dtype:
-        xc = xc.to(dtype)
-    xc = xc.contiguous()
-    if xc.data_ptr() % 16:
-        xc = xc.clone()  # a view at an odd offset: the entry loads 16 bytes at a time
+    xc = _rows(x, K, dtype, True)
     mats = (_lib.LoraMat * len(items))()
     for i, (y, A, B, scaling) in enumerate(items):
         mats[i] = _lib.LoraMat(A.data_ptr(), B.data_ptr(), y.data_ptr(), y.data_ptr(), int(B.shape[0]),
                                int(A.shape[0]), float(scaling))
-    with torch.cuda.device(dev):
-        rc = _lib.lib().nf4_lora_add(xc.data_ptr(), M, K, ctypes.cast(mats, ctypes.c_void_p), len(items),
-                                     _dtype_code(dtype), None, torch.cuda.current_stream().cuda_stream)
-    _lib.check(rc, "nf4 fused lora add")
+    _stream_call("nf4 fused lora add", x.device, _lib.lib().nf4_lora_add, xc.data_ptr(), M, K,
+                 ctypes.cast(mats, ctypes.c_void_p), len(items), _dtype_code(dtype), None)
 
 
 def _lora_base_in_place(y: torch.Tensor, dtype: torch.dtype) -> bool:
     return y.dtype == dtype and y.is_contiguous() and y.data_ptr() % 16 == 0 and not y.requires_grad
+
+
+def _adapters_grouped(x: torch.Tensor, modules: list, entries: list, biases, fusable, add, composite) -> List[torch.Tensor]:
+    """The skeleton of the grouped adapter functions, ``entries[i]`` being module i's adapter or stack
+    (None: it has none): the base through ``nf4_linear_bnb_grouped``, then ONE launch -- ``add(M, K, dtype,
+    [(y, *entry)])`` -- for all entries that are ``fusable(mod, entry, M)`` and whose base result can
+    be updated in place, when there are 1 .. ``LORA_GROUP_MAX`` of them; ``composite(y, entry)`` for
+    every other one."""
+    ys = nf4_linear_bnb_grouped(x, modules, biases)
+    if not modules:
+        return ys
+    K = int(modules[0].in_features)
+    M = x.numel() // K if K and x.shape[-1] == K else 0
+    dtype = modules[0].weight.quant_state.dtype
+    fused = [e is not None and int(mod.in_features) == K and mod.weight.quant_state.dtype == dtype
+             and fusable(mod, e, M) and _lora_base_in_place(y, dtype) for mod, e, y in zip(modules, entries, ys)]
+    if not 1 <= sum(fused) <= _lib.LORA_GROUP_MAX:
+        fused = [False] * len(modules)
+    items = [(y, e[0], e[1], e[2]) for y, e, f in zip(ys, entries, fused) if f]
+    if items:
+        add(M, K, dtype, items)
+    return [y if f or e is None else composite(y, e) for y, e, f in zip(ys, entries, fused)]
 
 
 def nf4_linear_lora_bnb(x: torch.Tensor, module, lora_A: torch.Tensor, lora_B: torch.Tensor, scaling: float,
@@ -1510,22 +1412,10 @@ def nf4_linear_lora_bnb_grouped(x: torch.Tensor, modules: Sequence, adapters: Se
     adapters = list(adapters)
     if len(adapters) != len(modules):
         raise ValueError("nf4_linear_lora_bnb_grouped: one adapter (or None) per module")
-    ys = nf4_linear_bnb_grouped(x, modules, biases)
-    if not modules:
-        return ys
-    K = int(modules[0].in_features)
-    M = x.numel() // K if K and x.shape[-1] == K else 0
-    dtype = modules[0].weight.quant_state.dtype
-    fused = [ad is not None and int(mod.in_features) == K and mod.weight.quant_state.dtype == dtype
-             and _lora_fusable(x, mod, ad[0], ad[1], M) and _lora_base_in_place(y, dtype)
-             for mod, ad, y in zip(modules, adapters, ys)]
-    if not 1 <= sum(fused) <= _lib.LORA_GROUP_MAX:
-        fused = [False] * len(modules)
-    items = [(y, ad[0], ad[1], ad[2]) for y, ad, f in zip(ys, adapters, fused) if f]
-    if items:
-        _lora_add(x, M, K, dtype, items)
-    return [y if f or ad is None else _lora_composite(y, x, ad[0], ad[1], ad[2])
-            for y, ad, f in zip(ys, adapters, fused)]
+    return _adapters_grouped(x, modules, adapters, biases,
+                             lambda mod, ad, M: _lora_fusable(x, mod, ad[0], ad[1], M),
+                             lambda M, K, dtype, items: _lora_add(x, M, K, dtype, items),
+                             lambda y, ad: _lora_composite(y, x, ad[0], ad[1], ad[2]))
 
 
 # Rows at which nf4_linear_multilora_bnb and nf4_linear_multilora_bnb_grouped take the routed
@@ -1598,20 +1488,11 @@ def _multilora_fusable(x: torch.Tensor, module, A: torch.Tensor, B: torch.Tensor
                        ids: torch.Tensor, M: int) -> bool:
     """nf4_linear_multilora_bnb's fused-path rules (its docstring) for one stack: _lora_fusable's,
     on [S, r, K] / [S, N, r]."""
-    dtype = module.weight.quant_state.dtype
     dev = module.weight.data.device
-    N, K = int(module.out_features), int(module.in_features)
-    S, r = int(A.shape[0]), int(A.shape[1])
-    return (dev.type == "cuda" and x.device == dev and A.device == dev and B.device == dev and ids.device == dev
-            and scaling.device == dev and scaling.dtype == torch.float32 and scaling.is_contiguous()
-            and dtype in (torch.float16, torch.bfloat16) and A.dtype == dtype and B.dtype == dtype
-            and max(1, MULTILORA_ROUTED_MIN_M) <= M <= min(MULTILORA_ROUTED_MAX_M, _lib.LORA_MAX_M)
-            and 1 <= S <= _lib.LORA_MAX_ADAPTERS and r % 8 == 0 and 8 <= r <= _lib.LORA_MAX_R
-            and K % 32 == 0 and K >= 32 and N % 16 == 0 and N >= 16
-            and A.is_contiguous() and B.is_contiguous() and A.data_ptr() % 16 == 0 and B.data_ptr() % 16 == 0
-            and scaling.data_ptr() % 4 == 0
-            and not (torch.is_grad_enabled() and (x.requires_grad or A.requires_grad or B.requires_grad
-                                                  or scaling.requires_grad)))
+    return (ids.device == dev and scaling.device == dev and scaling.dtype == torch.float32 and scaling.is_contiguous()
+            and scaling.data_ptr() % 4 == 0 and 1 <= int(A.shape[0]) <= _lib.LORA_MAX_ADAPTERS
+            and not (torch.is_grad_enabled() and scaling.requires_grad)
+            and _adapter_fusable(x, module, A, B, int(A.shape[1]), M, MULTILORA_ROUTED_MIN_M, MULTILORA_ROUTED_MAX_M))
 
 
 def _multilora_ids32(ids: torch.Tensor, S: int) -> torch.Tensor:
@@ -1626,23 +1507,14 @@ def _multilora_ids32(ids: torch.Tensor, S: int) -> torch.Tensor:
 def _multilora_add(x: torch.Tensor, M: int, K: int, dtype: torch.dtype, ids32: torch.Tensor, S: int, items) -> None:
     """ONE nf4_lora_add_routed launch: ``items`` is [(y [.., N] contiguous, updated in place, A [S, r, K],
     B [S, N, r], scaling fp32 [S])]."""
-    dev = x.device
-    xc = x.reshape(M, K)
-    if xc.dtype != dtype:
-        xc = xc.to(dtype)
-    xc = xc.contiguous()
-    if xc.data_ptr() % 16:
-        xc = xc.clone()  # a view at an odd offset: the entry loads 16 bytes at a time
+    xc = _rows(x, K, dtype, True)
     stacks = (_lib.LoraStack * len(items))()
     for i, (y, A, B, scaling) in enumerate(items):
         r, N = int(A.shape[1]), int(B.shape[1])
         stacks[i] = _lib.LoraStack(A.data_ptr(), B.data_ptr(), scaling.data_ptr(), y.data_ptr(), y.data_ptr(), N,
                                    r * K, N * r, r)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().nf4_lora_add_routed(xc.data_ptr(), ids32.data_ptr(), M, K, S,
-                                            ctypes.cast(stacks, ctypes.c_void_p), len(items), _dtype_code(dtype), None,
-                                            torch.cuda.current_stream().cuda_stream)
-    _lib.check(rc, "nf4 routed lora add")
+    _stream_call("nf4 routed lora add", x.device, _lib.lib().nf4_lora_add_routed, xc.data_ptr(), ids32.data_ptr(), M, K,
+                 S, ctypes.cast(stacks, ctypes.c_void_p), len(items), _dtype_code(dtype), None)
 
 
 def nf4_linear_multilora_bnb(x: torch.Tensor, module, lora_A: torch.Tensor, lora_B: torch.Tensor, scaling,
@@ -1709,21 +1581,9 @@ def nf4_linear_multilora_bnb_grouped(x: torch.Tensor, modules: Sequence, stacks:
             continue
         _multilora_check(x, mod, st[0], st[1], adapter_ids)
         checked.append((st[0], st[1], _multilora_scaling(st[2], int(st[0].shape[0]), st[0].device)))
-    ys = nf4_linear_bnb_grouped(x, modules, biases)
-    if not modules:
-        return ys
-    K = int(modules[0].in_features)
-    M = x.numel() // K if K and x.shape[-1] == K else 0
-    dtype = modules[0].weight.quant_state.dtype
-    S = next((int(st[0].shape[0]) for st in checked if st is not None), 0)
-    fused = [st is not None and int(mod.in_features) == K and mod.weight.quant_state.dtype == dtype
-             and int(st[0].shape[0]) == S and _multilora_fusable(x, mod, st[0], st[1], st[2], adapter_ids, M)
-             and _lora_base_in_place(y, dtype)
-             for mod, st, y in zip(modules, checked, ys)]
-    if not 1 <= sum(fused) <= _lib.LORA_GROUP_MAX:
-        fused = [False] * len(modules)
-    items = [(y, st[0], st[1], st[2]) for y, st, f in zip(ys, checked, fused) if f]
-    if items:
-        _multilora_add(x, M, K, dtype, _multilora_ids32(adapter_ids, S), S, items)
-    return [y if f or st is None else _multilora_composite(y, x, st[0], st[1], st[2], adapter_ids)
-            for y, st, f in zip(ys, checked, fused)]
+    S = next((int(st[0].shape[0]) for st in checked if st is not None), 0)  # the launch takes stacks of one size
+    return _adapters_grouped(
+        x, modules, checked, biases,
+        lambda mod, st, M: int(st[0].shape[0]) == S and _multilora_fusable(x, mod, st[0], st[1], st[2], adapter_ids, M),
+        lambda M, K, dtype, items: _multilora_add(x, M, K, dtype, _multilora_ids32(adapter_ids, S), S, items),
+        lambda y, st: _multilora_composite(y, x, st[0], st[1], st[2], adapter_ids))
