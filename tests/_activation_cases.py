@@ -19,7 +19,9 @@ without any of those suites noticing:
                fp32 partial can overflow
 
 ``special_x`` places them on both sides of a 16-row tile edge and on the last row (rows 0, M-1,
-15, 16 where M admits), never on every row.  ``judge`` compares an output with the float64
+15, 16 where M admits), never on every row -- or on the rows its caller names (``at``: the
+row-block expert GEMM's case, ``moe_rb_routing``, puts them on both sides of a row-block edge of
+one expert's pair list).  ``judge`` compares an output with the float64
 reference by class -- finite within the suites' own bound (``_gemm_cases.tol``, unchanged), the
 reference's infinity, NaN -- and ``isolated`` demands that every row not replaced is bitwise what
 the same call gives on the plain draw: nothing of a special row may reach a neighbour.
@@ -128,18 +130,22 @@ def _huge_row(base64, ws64, dt):
     return bits
 
 
-def special_x(M, K, dt, seed, kinds, w_bits):
+def special_x(M, K, dt, seed, kinds, w_bits, at=None):
     """(x_bits, base_bits, rows): ``base_bits`` [M, K] the ordinary ``_gemm_cases.x_bits`` draw,
     ``x_bits`` the same with ``len(kinds)`` rows replaced, ``rows`` {row: kind}.  ``w_bits``: the
     16-bit matrix [N, K] of the weight in use, or a list of them (a group, the experts); the
-    conditions on k0 and on the ``huge`` power hold for each.  At M = 1 one kind at a time."""
+    conditions on k0 and on the ``huge`` power hold for each.  At M = 1 one kind at a time.
+    ``at``: the rows to replace, in the order of ``kinds`` (default: ``positions(M, len(kinds))``)."""
     ws = [w_bits] if isinstance(w_bits, np.ndarray) else list(w_bits)
     ws64 = [bits_to_f64(np.asarray(w, np.uint16), dt) for w in ws]
     assert all(w.shape[1] == K and np.isfinite(w).all() for w in ws64)
     base = x_bits(M, K, dt, seed)[1].copy()
     x = base.copy()
     rng = np.random.default_rng(seed)
-    rows = dict(zip(positions(M, len(kinds)), kinds))
+    if at is None:
+        at = positions(M, len(kinds))
+    assert len(at) >= len(kinds) and len(set(at)) == len(at) and all(0 <= r < M for r in at), (M, at, kinds)
+    rows = dict(zip(at, kinds))
     for r, kind in rows.items():
         b64 = bits_to_f64(base[r], dt)
         if kind == "nan":
@@ -238,6 +244,7 @@ GROUPED_REF = {"Ns": (128, 64, 64), "K": 2048, "Ms": (1, 8)}     # M = 1: the gr
 GROUPED_BNB = {"Ns": (64, 192, 64), "K": 2048, "Ms": (1, 16)}
 MT = {"N": 192, "K": 768, "Ms": (17, 33, 100)}
 MOE = {"E": 4, "N": 192, "K": 768, "P": 33, "x_div": 2}
+MOE_RB = {"P": 300, "x_div": 2}   # nf4_gemm_bnb_moe_rb on the MOE stack: three row blocks in the grid
 SWIGLU = {"I": 192, "K": 1152, "M": 48}
 API_LINEAR = {"N": 128, "K": 1024, "Ms": (1, 32, 33, 128, 129)}
 DRAWN_SCALE = 32.0  # drawn nested statistics times 2^5: outputs of about 16 for N(0, 1) activations
@@ -267,6 +274,39 @@ def decode_cfgs(M, reference_mode):
 
 def x_seed(M, K):
     return 1000 + 7 * M + K
+
+
+def moe_rb_routing():
+    """(ids[300], special tokens) of the row-block case (test_gpu_gemm_moe_rb_activations.py): 150
+    tokens of two pairs.  Every token has one pair on expert 1 -- its odd pair, its even one where
+    t % 7 == 0 -- and tokens 0 .. 8 both, so expert 1's ascending list has 159 entries: row block 0
+    full, row block 1 with 31 rows (a partly filled last row tile), its entries 127 and 128 (the last
+    staged row of block 0, the first of block 1) in the middle of a ballot round, in tokens 118 and
+    119, and its last entry pair 299 = P - 1.  The other pairs go round experts 0, 2, 3 (at least
+    45 each: at least 20 rows per pair of any one special token in every expert's subset, so with
+    one ``huge`` token no subset's borderline share can exceed BORDERLINE_CAP whatever the values),
+    but token 118's, which has the invalid id E, and plain token 60's, which has -1.  The special
+    tokens, in the order of the kinds: 118, 119, 149 (last entry, pair P - 1), 0 (pair 0)."""
+    E, P = MOE["E"], MOE_RB["P"]
+    ids = np.empty(P, np.int64)
+    other = 0
+    for t in range(P // 2):
+        mine, rest = (2 * t, 2 * t + 1) if t % 7 == 0 else (2 * t + 1, 2 * t)
+        ids[mine] = 1
+        if t < 9:
+            ids[rest] = 1
+        else:
+            ids[rest] = (0, 2, 3)[other % 3]
+            other += 1
+    ids[2 * 118] = E
+    ids[2 * 60 + (60 % 7 == 0)] = -1
+    return ids, [118, 119, 149, 0]
+
+
+def moe_rb_passes(kinds, tokens):
+    """The orders in which a kind set goes onto the special tokens: a set with fewer kinds than
+    tokens runs a second time from the other end, so that every special token gets a kind."""
+    return [list(tokens)] if len(kinds) >= len(tokens) else [list(tokens), list(tokens)[::-1]]
 
 
 def kind_sets(M, dt, which):

@@ -180,3 +180,61 @@ def test_every_gpu_case_builds_and_keeps_its_borderline_share(coracle, dt):
         for K, cfg in A.decode_cfgs(M, True):
             assert cfg is None or cfg in {cfg_tuple(c) for c in gemm_cfgs(K, M)}, (M, K, cfg)
     assert A.positions(32, 4) == [0, 31, 15, 16] and A.positions(17, 3) == [0, 16, 15] and A.positions(8, 4) == [0, 7, 1, 6]
+
+
+def test_the_row_block_routing_is_what_it_says():
+    """moe_rb_routing: the special tokens sit on entries 127 / 128 and on the last entry of expert
+    1's ascending pair list, on pair 0 and on pair P - 1; the block edge lies inside a ballot round;
+    one special token owns an invalid id; every expert's subset holds at least 20 rows per pair of
+    any one special token (the condition under which the borderline cap cannot be exceeded)."""
+    E, P, x_div = A.MOE["E"], A.MOE_RB["P"], A.MOE_RB["x_div"]
+    ids, tokens = A.moe_rb_routing()
+    assert ids.shape == (P,) and P == 300 and x_div == 2 and len(set(tokens)) == len(tokens) == 4
+    tok = np.arange(P) // x_div
+    valid = (ids >= 0) & (ids < E)
+    assert set(ids[~valid].tolist()) == {-1, E}
+    mine = np.nonzero(ids == 1)[0]                             # expert 1's ascending list
+    assert mine.size >= 140 and 128 < mine.size < 256 and mine.size % 16, "two row blocks, the last row tile partly filled"
+    assert [int(tok[mine[127]]), int(tok[mine[128]]), int(tok[mine[-1]]), int(tok[0])] == tokens
+    assert tok[mine[127]] != tok[mine[128]] and mine[-1] == P - 1 and tok[P - 1] in tokens
+    assert mine[127] % 64 != 63 and mine[127] // 64 == mine[128] // 64, "the block edge in the middle of a ballot round"
+    assert any(not valid[p] for p in range(P) if tok[p] in tokens), "no invalid id on a special token"
+    assert any(not valid[p] for p in range(P) if tok[p] not in tokens), "no invalid id on a plain token"
+    counts = np.bincount(ids[valid], minlength=E)
+    assert (counts > 0).all()
+    for e in range(E):
+        for t in tokens:  # whichever special token is the huge one
+            assert counts[e] >= 20 * max(1, int(((ids == e) & (tok == t)).sum())), (e, t, counts)
+    kinds4, kinds3 = A.FINITE["f16"], A.NONFINITE
+    assert A.moe_rb_passes(kinds4, tokens) == [tokens]
+    assert {t for at in A.moe_rb_passes(kinds3, tokens) for t in at[:3]} == set(tokens)
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+def test_the_row_block_case_builds_and_keeps_its_borderline_share(coracle, dt):
+    """The reference alone, per expert subset as test_gpu_gemm_moe_rb_activations.py judges it:
+    special_x's own assertions hold on the named rows and the borderline share stays under the cap."""
+    import torch
+
+    from test_gpu_gemm_moe import _Stack
+
+    E, N, K, P, x_div = A.MOE["E"], A.MOE["N"], A.MOE["K"], A.MOE_RB["P"], A.MOE_RB["x_div"]
+    S = _Stack(coracle, torch.device("cpu"), "nested", "sensitive", E, N, K, dt)
+    ids, tokens = A.moe_rb_routing()
+    T = P // x_div
+    tok = np.arange(P) // x_div
+    shares = []
+    for which in ("finite", "nonfinite"):
+        for kinds in A.kind_sets(T, dt, which):
+            for at in A.moe_rb_passes(kinds, tokens):
+                x, base, rows = A.special_x(T, K, dt, A.x_seed(T, K), kinds, S.bits, at=at)
+                assert list(rows) == at[:len(kinds)] and (x != base).any(axis=1).sum() == len(kinds)
+                for e in range(E):
+                    sel = np.nonzero(ids == e)[0]
+                    s = A.borderline_share(x[tok[sel]], S.bits[e], dt)
+                    assert s <= A.BORDERLINE_CAP, (dt, kinds, e, s)
+                    shares.append(s)
+                    assert A.borderline_share(base[tok[sel]], S.bits[e], dt) == 0.0
+    print(f"row-block case {dt}: borderline share at most {max(shares):.4%} over {len(shares)} (pass, expert) subsets")
+    if dt == "bf16":
+        assert max(shares) == 0.0

@@ -10,6 +10,8 @@ nf4_gemm_check_workspace is clean.
 
 Shapes: E = 4 (once 256), N = 64 or 128, K = 256 -- two 128-deep chunks, so one and two K slices
 both exist; the pair counts sit on the edges of the 128-row blocks and of the 64-id ballot rounds.
+The exact-weight test walks the identity at 1024 pairs; every other shape, stack form, K-slice count
+and routing is drawn: test_gpu_gemm_moe_rb_drawn.py.
 """
 import ctypes
 
@@ -164,6 +166,39 @@ def test_every_row_has_the_bits_of_the_128_pair_entry(coracle, gpu, waves, kspli
         for rb_cfg, moe_cfg in ((_cfg(waves, ksplit), _cfg(waves, ksplit, MOE.MOE)), (None, None)):
             a, b = _rb(S, xq, small, 2, rb_cfg), MOE._moe(S, xq, small, 2, moe_cfg)
             assert torch.equal(a.view(torch.int16), b.view(torch.int16)), f"{Q} pairs, cfg {_tag(rb_cfg)}"
+
+
+# ---- exact weights ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+def test_exact_walk_at_1024_pairs_recovers_every_experts_weights(coracle, gpu, dt):
+    """E = 4 weights of 128 x 256 (sensitive nested, blocksize2 16; drawn single) and P = 1024:
+    every (expert, k) exactly once in ONE launch.  x_div 1: a drawn permutation of the (e, k) with
+    x[p] = eye[k_p]; x_div 4: x = eye(256) and each token's four ids a drawn permutation of
+    0 .. 3.  y[p] is W_{e_p}[:, k_p] plus exact zeros and must equal the oracle's 16-bit weight by
+    value, with no tolerance -- a slice that sums an exact value and exact zeros stays exact, so
+    also under two K slices.  Each expert holds 256 rows: two full row blocks, and row blocks 2 .. 7
+    of every expert return without a row.  A swapped expert, row block, list entry, column or k
+    shows, and so does a fused multiply-add in the scale."""
+    E, N, P = 4, 128, 1024
+    tdt = MOE._tdt(dt)
+    rng = np.random.default_rng(1024)
+    eye = torch.eye(K, dtype=tdt, device=gpu)
+    perm = rng.permutation(P)
+    forms = [(1, perm // K, perm % K), (4, np.concatenate([rng.permutation(E) for _ in range(K)]), np.arange(P) // 4)]
+    for x_div, ids, ks in forms:
+        assert sorted(zip(ids.tolist(), ks.tolist())) == [(e, k) for e in range(E) for k in range(K)]
+    edge = [int(np.nonzero(forms[0][1] == e)[0][127]) % 64 for e in range(E)]
+    assert any(lane != 63 for lane in edge), "no block edge inside a ballot round"
+    for S in (MOE._stack(coracle, gpu, "nested", "sensitive", E, N, K, dt), MOE._stack(coracle, gpu, "single", "drawn", E, N, K, dt)):
+        want = torch.stack([torch.from_numpy(np.ascontiguousarray(b).view(np.int16)).to(gpu).view(tdt) for b in S.bits])  # [E, N, K]
+        for x_div, ids, ks in forms:
+            kt = torch.from_numpy(ks).to(gpu)
+            x = (eye[kt] if x_div == 1 else eye).contiguous()
+            expect = want[torch.from_numpy(ids).to(gpu), :, kt]                                                           # [P, N]
+            for cfg in (None, _cfg(2, 1), _cfg(2, 2), _cfg(4, 2)):
+                ok = _rb(S, x, ids, x_div, cfg) == expect
+                assert bool(ok.all()), (f"{S.mode} {dt} x_div {x_div} cfg {_tag(cfg)}: {int((~ok).sum())} of {ok.numel()} weights "
+                                        f"differ, first at (pair, n) {(~ok).nonzero()[0].tolist()}")
 
 
 # ---- reproducible and re-entrant -------------------------------------------------------------------

@@ -30,6 +30,12 @@ every call twice, the suites' own judges).  Round r draws ``--seed`` + r for eac
 (entry, dtype) sequences; ``--cases`` counts calls over all rounds.  One JSON line per failing case
 with its fields.
 
+``--semantics moe_rb``: the expert GEMM in row blocks (nf4_gemm_bnb_moe_rb, 1 .. 1024 pairs) on the drawn
+calls of tests/_moe_rb_draws.py, run and judged exactly as tests/test_gpu_gemm_moe_rb_drawn.py does (its
+``Runner``: one workspace per dtype sequence, every call twice, test_gpu_gemm_moe.py's judge, and
+nf4_gemm_bnb_moe's bits on subsets of at most 128 pairs).  Round r draws ``--seed`` + r for both dtypes;
+``--cases`` counts calls over all rounds, ``launches`` every launch of either entry.
+
 ``--semantics lora``: the fused adapter launch (nf4_lora_add) on the drawn grouped calls of
 tests/_lora_draws.py, run and judged exactly as tests/test_gpu_lora_drawn.py does (its ``Runner``: all
 outputs of a call in one allocation with sentinel gaps, every call twice, the float64 chain's bound).
@@ -252,6 +258,41 @@ def family_sweep(args, orc, dev):
                                   "seed": args.seed, "seconds": round(time.time() - t0, 1)}}), flush=True)
 
 
+def moe_rb_sweep(args, orc, dev):
+    """--semantics moe_rb: rounds of the two drawn sequences until --cases or --seconds is reached."""
+    import _moe_rb_draws as D
+    import test_gpu_gemm_family_drawn as FT
+    import test_gpu_gemm_moe_rb_drawn as T
+
+    t0 = time.time()
+    done = bad = rounds = launches = 0
+    per_dtype = {dt: 0 for dt in D.DTYPES}
+    while done < args.cases and time.time() - t0 <= args.seconds:
+        seed = args.seed + rounds
+        for dt in D.DTYPES:
+            cases = D.draws(dt, seed)
+            runner = T.Runner(dt, orc, dev)
+            runner.prepare(cases)
+            for c in cases:
+                if done >= args.cases or time.time() - t0 > args.seconds:
+                    break
+                try:
+                    runner.run(c)
+                except AssertionError as e:
+                    bad += 1
+                    print(json.dumps({"mismatch": dict(c.fields(), semantics="moe_rb", error=str(e).split("\n", 1)[-1][:400])}),
+                          flush=True)
+                done += 1
+                per_dtype[dt] += 1
+            launches += runner.launches
+        FT._STACKS.clear()  # the next round's pool
+        rounds += 1
+        print(json.dumps({"progress": done, "mismatches": bad, "rounds": rounds, "seconds": round(time.time() - t0, 1)}), flush=True)
+    print(json.dumps({"summary": {"semantics": "moe_rb", "cases": done, "launches": launches, "per_dtype": per_dtype,
+                                  "rounds": rounds, "mismatches": bad, "seed": args.seed, "seconds": round(time.time() - t0, 1)}}),
+          flush=True)
+
+
 def lora_sweep(args, dev):
     """--semantics lora / lora_routed: rounds of the two drawn sequences until --cases or --seconds is reached."""
     routed = args.semantics == "lora_routed"
@@ -290,9 +331,10 @@ def lora_sweep(args, dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--semantics", choices=["ref", "bnb", "family", "lora", "lora_routed"], default="ref",
+    ap.add_argument("--semantics", choices=["ref", "bnb", "family", "moe_rb", "lora", "lora_routed"], default="ref",
                     help="ref: nf4_gemm_ref and its kin; bnb: nf4_gemm_bnb / nf4_gemm_bnb_single on nf4_quantize's weights; "
                          "family: the row-tiled and expert GEMMs on the drawn cases of tests/_family_draws.py; "
+                         "moe_rb: nf4_gemm_bnb_moe_rb on the drawn calls of tests/_moe_rb_draws.py; "
                          "lora: nf4_lora_add on the drawn grouped calls of tests/_lora_draws.py; "
                          "lora_routed: nf4_lora_add_routed on the drawn calls of tests/_lora_routed_draws.py")
     ap.add_argument("--cases", type=int, default=1500)
@@ -312,6 +354,8 @@ def main():
     orc = O.COracle()
     if args.semantics == "family":
         return family_sweep(args, orc, dev)
+    if args.semantics == "moe_rb":
+        return moe_rb_sweep(args, orc, dev)
     rng = np.random.default_rng(args.seed)
     t0 = time.time()
     done = bad = cfg_runs = grouped_runs = 0
