@@ -557,6 +557,48 @@ int nf4_gemm_bnb_moe_rb(const void* x, const void* expert_ids, int64_t P, int32_
                         void* y, int32_t out_dtype, void* workspace, size_t workspace_bytes,
                         const nf4_gemm_cfg* cfg, void* hip_stream);
 
+/* The fused GEMM in bitsandbytes semantics for a prompt (prefill): nf4_gemm_bnb_mt's product,
+ * argument lists, alignments and status codes for 1 <= M <= NF4DQ_GEMM_PF_MAX_M rows in ONE
+ * launch, with no 16-bit copy of the weight and no host read of the offset.  W is bit for bit
+ * what nf4_dequant_bnb / nf4_dequant_bnb_single write, accumulation is fp32 on MFMA, one final
+ * rounding to out_dtype.  A workgroup owns a block of 128 or 256 rows, 128 columns and one K
+ * slice; per 64-deep K step it decodes its 128 x 64 weights once into LDS, where all of its
+ * waves read them.  The whole row range is taken (so that block edges can be tested); up to 128
+ * rows nf4_gemm_bnb_mt is the faster entry.
+ * Differences from nf4_gemm_bnb_mt's rules: N % 128 == 0 and N >= 128 (else NF4DQ_ERR_SHAPE);
+ * M > NF4DQ_GEMM_PF_MAX_M: NF4DQ_ERR_SHAPE; M == 0 (all else valid): NF4DQ_OK, nothing
+ * launched; M*K*2, M*N*2 or packed_len reaching 2^31, more split-K tickets (row blocks x column
+ * tiles) than the workspace header holds or a workspace need reaching 2^32 bytes:
+ * NF4DQ_ERR_TOO_LARGE.
+ * cfg NULL = the library's choice from (M, N, K, CU count) alone.  A cfg names kernel
+ * NF4DQ_GEMM_PF (0 = the same) with
+ *   waves   waves per workgroup, 4 / 8: row blocks of 128 / 256 rows
+ *   depth   1
+ *   ksplit  K slices, 1 .. min(K / 64, 16); ceil(K/64 / ksplit) steps per slice, so the last
+ *           slices may be short or empty
+ *   strips  0
+ * and never falls back: an invalid one, NF4DQ_GEMM_MT included, is NF4DQ_ERR_ARG.
+ * Workspace (nf4_gemm_bnb_pf_workspace_bytes; 0 = none, one K slice): nf4_gemm_bnb_mt's layout
+ * and contract -- the ticket header, then ksplit slabs of M * N floats, all zero between calls,
+ * shareable with the other fused entries on the same stream.  One ticket per (row block, column
+ * tile); the slice drawing the last one sums the slabs in slice order.  No workgroup waits for
+ * another.  The result is a function of the inputs and the cfg alone, and under one cfg a row's
+ * bits do not depend on M or on the other rows.
+ * Asynchronous on `hip_stream`; one launch; allocates nothing; capturable in a graph. */
+#define NF4DQ_GEMM_PF_MAX_M 8192
+#define NF4DQ_GEMM_PF 14
+size_t nf4_gemm_bnb_pf_workspace_bytes(int64_t M, int64_t N, int64_t K, const nf4_gemm_cfg* cfg);
+int nf4_gemm_bnb_pf(const void* x, int64_t M, const uint8_t* packed, int64_t packed_len,
+                    const uint8_t* absmax_q, int64_t nb, const float* code2,
+                    const float* absmax2, int64_t n2, const float* offset,
+                    int32_t blocksize, int32_t blocksize2,
+                    void* y, int32_t out_dtype, int64_t N, int64_t K,
+                    void* workspace, size_t workspace_bytes, const nf4_gemm_cfg* cfg, void* hip_stream);
+int nf4_gemm_bnb_pf_single(const void* x, int64_t M, const uint8_t* packed, int64_t packed_len,
+                           const float* absmax, int64_t nabs, int32_t blocksize,
+                           void* y, int32_t out_dtype, int64_t N, int64_t K,
+                           void* workspace, size_t workspace_bytes, const nf4_gemm_cfg* cfg, void* hip_stream);
+
 /* The first half of a Llama-family MLP, `silu(gate(x)) * up(x)`, in bitsandbytes semantics for
  * 1..128 rows: ONE launch of the row-tiled family over the gate and the up weight, which share
  * x and the shape [I][K].  With dt = out_dtype (fp16 / bf16) and rn = round-to-nearest-even to dt,

@@ -37,6 +37,7 @@ IDS_I32 = 0
 IDS_I64 = 1
 GEMM_MAX_M = 32
 GEMM_MT_MAX_M = 128  # NF4DQ_GEMM_MT_MAX_M: rows of the row-tiled entries (nf4_gemm_bnb_mt*)
+GEMM_PF_MAX_M = 8192  # NF4DQ_GEMM_PF_MAX_M: rows of the prefill entries (nf4_gemm_bnb_pf*)
 
 
 class MatrixDesc(ctypes.Structure):
@@ -83,6 +84,7 @@ GEMM_MT_SWIGLU = 10  # the fused gate/up SwiGLU launch (nf4_gemm_bnb_mt_swiglu);
 GEMM_MOE_SWIGLU = 11  # the fused expert SwiGLU launch (nf4_gemm_bnb_moe_swiglu); its own entry only
 GEMM_MOE_DOWN = 12  # the fused expert down projection with the routed sum (nf4_gemm_bnb_moe_down); its own entry only
 GEMM_MOE_RB = 13  # the expert GEMM in row blocks, up to MOE_RB_MAX_PAIRS pairs (nf4_gemm_bnb_moe_rb); its own entry only
+GEMM_PF = 14  # the prefill GEMM in row blocks of 128 / 256 rows (nf4_gemm_bnb_pf*: up to GEMM_PF_MAX_M rows); its own entries only
 ACT_SILU = 0  # NF4DQ_ACT_SILU: the activation of nf4_gemm_bnb_mt_swiglu and nf4_gemm_bnb_moe_swiglu
 MOE_MAX_PAIRS = 128    # NF4DQ_MOE_MAX_PAIRS: (token, choice) pairs of one nf4_gemm_bnb_moe launch
 MOE_RB_MAX_PAIRS = 1024  # NF4DQ_MOE_RB_MAX_PAIRS: (token, choice) pairs of one nf4_gemm_bnb_moe_rb launch
@@ -203,6 +205,11 @@ SIGNATURES = {
     "nf4_gemm_bnb_mt": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _P, _I32, _I32, _P, _I32, _I64, _I64,
                                        _P, ctypes.c_size_t, ctypes.POINTER(GemmCfg), _P]),
     "nf4_gemm_bnb_mt_single": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _I32, _P, _I32, _I64, _I64, _P,
+                                              ctypes.c_size_t, ctypes.POINTER(GemmCfg), _P]),
+    "nf4_gemm_bnb_pf_workspace_bytes": (ctypes.c_size_t, [_I64, _I64, _I64, ctypes.POINTER(GemmCfg)]),
+    "nf4_gemm_bnb_pf": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _P, _I32, _I32, _P, _I32, _I64, _I64,
+                                       _P, ctypes.c_size_t, ctypes.POINTER(GemmCfg), _P]),
+    "nf4_gemm_bnb_pf_single": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _I32, _P, _I32, _I64, _I64, _P,
                                               ctypes.c_size_t, ctypes.POINTER(GemmCfg), _P]),
     # `experts`: const void* in the header, pointing at ONE MoeExperts; `expert_ids`: int32 on the device
     "nf4_gemm_bnb_moe_workspace_bytes": (ctypes.c_size_t, [_I64, _P, ctypes.POINTER(GemmCfg)]),

@@ -710,6 +710,86 @@ def _bnb_gemm_blocksizes(qs) -> bool:
     return True
 
 
+# Rows at which nf4_linear_bnb takes the prefill launch (nf4_linear_bnb_prefill) above
+# GEMM_MT_ROUTED_M rows.  The range ships EMPTY: past 128 rows nf4_linear_bnb keeps dequantize +
+# matmul, which is the faster route at most measured shapes (profiles/gemm_pf/).  A
+# caller who wants every Linear4bit.forward of a prompt fused and capturable -- no host read of the
+# offset, no 16-bit copy of the weight -- sets GEMM_PF_ROUTED_MAX_M = 8192.
+GEMM_PF_ROUTED_MIN_M = 1
+GEMM_PF_ROUTED_MAX_M = 0
+
+
+def _bnb_prefill_fusable(x: torch.Tensor, module, M: int) -> bool:
+    """nf4_linear_bnb's fused-path rules at the prefill entry's shapes: 1..GEMM_PF_MAX_M rows,
+    N % 128 == 0, blocksize 64, a 16-byte-aligned packed weight, and x, y and the packed weight
+    within the entry's 32-bit byte offsets (NF4DQ_ERR_TOO_LARGE there: the composite here)."""
+    qs = module.weight.quant_state
+    qweight = module.weight.data
+    N, K = int(module.out_features), int(module.in_features)
+    return (qweight.device.type == "cuda" and qs.dtype in (torch.float16, torch.bfloat16)
+            and 0 < M <= _lib.GEMM_PF_MAX_M and N >= 128 and N % 128 == 0 and K >= 128 and K % 128 == 0
+            and N <= 1 << 18 and K <= 1 << 24 and max(M * N * 2, M * K * 2, N * K // 2) < 1 << 31
+            and qweight.dtype == torch.uint8 and qweight.numel() == N * K // 2
+            and getattr(qs, "quant_type", None) == "nf4" and int(qs.blocksize) == 64 and _bnb_gemm_blocksizes(qs)
+            and qweight.data_ptr() % 16 == 0 and not (torch.is_grad_enabled() and x.requires_grad))
+
+
+def nf4_linear_bnb_prefill(x: torch.Tensor, module, bias: Optional[torch.Tensor] = None,
+                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``nf4_linear_bnb`` for a prompt: ``x @ W.t() (+ bias)`` in ONE fused launch for 1 ..
+    ``GEMM_PF_MAX_M`` (8192) rows (``nf4_gemm_bnb_pf`` / ``nf4_gemm_bnb_pf_single``).
+
+    W is what ``dequantize_nf4_bnb(module)`` returns, bit for bit, but it is never written: a
+    workgroup decodes each 128 x 64 weight tile once into LDS and multiplies it with a block of
+    128 or 256 rows, fp32 accumulation, one rounding.  The offset is read on the device, so the
+    call makes no host read and can be captured in a graph.  Taken under ``nf4_linear_bnb``'s
+    fused-path rules -- GPU, fp16 / bf16, nf4, uint8 packed weight of N * K / 2 bytes, no gradient
+    being recorded for ``x`` -- with blocksize 64, N % 128 == 0, K % 128 == 0 and a 16-byte-aligned
+    weight; everything else takes ``nf4_linear_bnb``.  The bias is added in torch behind the
+    launch.  ``out=`` takes a contiguous tensor of the result's shape and dtype.
+    """
+    qweight = module.weight.data
+    dtype = module.weight.quant_state.dtype
+    N, K = int(module.out_features), int(module.in_features)
+    if qweight.device.type == "cuda":
+        _same_device(x, qweight)
+    if x.shape[-1] != K:
+        raise RuntimeError(f"nf4_linear_bnb_prefill: x has {x.shape[-1]} features, weight expects {K}")
+    lead, M = _lead_rows(x, K)
+    if not _bnb_prefill_fusable(x, module, M):
+        return _into(out, nf4_linear_bnb(x, module, bias))
+    return _bnb_prefill_launch(x, module, bias, out, lead, M)
+
+
+def _bnb_prefill_launch(x: torch.Tensor, module, bias, out, lead, M: int) -> torch.Tensor:
+    """The launch of ``nf4_linear_bnb_prefill`` for a call ``_bnb_prefill_fusable`` has passed."""
+    qweight = module.weight.data
+    dtype = module.weight.quant_state.dtype
+    N, K = int(module.out_features), int(module.in_features)
+    dev = qweight.device
+    _check_out("nf4_linear_bnb_prefill", out, [*lead, N], dtype, dev)
+    direct = out is not None and bias is None and out.data_ptr() % 8 == 0  # the launch stores into out itself
+    y = out.view(M, N) if direct else torch.empty((M, N), dtype=dtype, device=dev)
+    xc = _rows(x, K, dtype, True)
+    L = _lib.lib()
+    keep = []
+    qs = module.weight.quant_state
+    entry = "nf4_gemm_bnb_pf"
+    stats = _bnb_stats("nf4_linear_bnb_prefill", qs, dev, keep)
+    if not _bnb_nested(qs):
+        entry += "_single"
+        stats = (stats[3], stats[4], stats[6])  # the single entries take (absmax, its count, blocksize) alone
+    args = (xc.data_ptr(), M, *_operand(qweight, None, keep), *stats, y.data_ptr(), _dtype_code(dtype), N, K)
+    _fused_call("nf4 fused bnb prefill gemm", dev, getattr(L, entry), args, L.nf4_gemm_bnb_pf_workspace_bytes,
+                (M, N, K, None))
+    if direct:
+        return out
+    y = y.reshape(*lead, N)
+    if bias is not None:
+        y = y + bias.to(y.dtype)
+    return _into(out, y)
+
+
 def nf4_linear_bnb(x: torch.Tensor, module, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``x @ W.t() (+ bias)`` for a ``Linear4bit`` weight W in bitsandbytes semantics.
 
@@ -728,8 +808,10 @@ def nf4_linear_bnb(x: torch.Tensor, module, bias: Optional[torch.Tensor] = None)
     is 64: again one launch, no host read of the offset, capturable.  Everything else --
     a gradient being recorded for ``x``, other block sizes above ``GEMM_MAX_M`` rows, CPU
     tensors, more rows than ``GEMM_MT_ROUTED_M`` -- dequantizes with the HIP kernel and
-    multiplies with torch, which autograd follows.  All paths use the same weights and fp32
-    accumulation; the summation order differs, so the last bit of ``y`` may.
+    multiplies with torch, which autograd follows.  More rows than ``GEMM_MT_ROUTED_M`` within
+    ``GEMM_PF_ROUTED_MIN_M .. GEMM_PF_ROUTED_MAX_M`` take ``nf4_linear_bnb_prefill``'s launch under
+    its rules; that range ships empty and is the caller's to open.  All paths use the same
+    weights and fp32 accumulation; the summation order differs, so the last bit of ``y`` may.
     """
     weight = module.weight
     qs = weight.quant_state
@@ -741,6 +823,9 @@ def nf4_linear_bnb(x: torch.Tensor, module, bias: Optional[torch.Tensor] = None)
     if x.shape[-1] != K:
         raise RuntimeError(f"nf4_linear_bnb: x has {x.shape[-1]} features, weight expects {K}")
     lead, M = _lead_rows(x, K)
+    if (M > GEMM_MT_ROUTED_M and GEMM_PF_ROUTED_MIN_M <= M <= GEMM_PF_ROUTED_MAX_M
+            and _bnb_prefill_fusable(x, module, M)):
+        return _bnb_prefill_launch(x, module, bias, None, lead, M)
     fused = (qweight.device.type == "cuda" and dtype in (torch.float16, torch.bfloat16)
              and 0 < M <= GEMM_MT_ROUTED_M and N % 64 == 0 and K % 128 == 0
              and qweight.dtype == torch.uint8 and qweight.numel() == N * K // 2
