@@ -599,6 +599,49 @@ int nf4_gemm_bnb_pf_single(const void* x, int64_t M, const uint8_t* packed, int6
                            void* y, int32_t out_dtype, int64_t N, int64_t K,
                            void* workspace, size_t workspace_bytes, const nf4_gemm_cfg* cfg, void* hip_stream);
 
+/* The input gradient of a frozen NF4 linear layer: dx[M][K] = g[M][N] . W[N][K] for
+ * 1 <= M <= NF4DQ_GEMM_PF_MAX_M rows in ONE launch, with no 16-bit copy of the weight and no
+ * host read of the offset.  W is bit for bit what nf4_dequant_bnb / nf4_dequant_bnb_single
+ * write, accumulation is fp32 on MFMA, one final rounding to out_dtype.  The base weight of a
+ * QLoRA layer has no gradient of its own, so this product is the layer's whole backward.
+ * nf4_gemm_bnb_pf's argument list with g [M][N] in x's place and dx [M][K] in y's, its
+ * alignments (g and packed 16 bytes, dx 8) and its status codes in its order.  A workgroup owns
+ * a block of 128 or 256 rows of g, 128 output columns and one slice of N; per step of 64 weight
+ * rows it stages their 64 x 64 packed bytes raw in LDS, forms the step's 128 block scales once
+ * and decodes the tile transposed ([128 k][64 n]) once, where all of its waves read it.
+ * Rules: blocksize == 64 (a larger valid one: NF4DQ_ERR_SHAPE); K % 128 == 0 and K >= 128,
+ * N % 64 == 0 and N >= 64 (N need not be a multiple of 128), M <= NF4DQ_GEMM_PF_MAX_M, else
+ * NF4DQ_ERR_SHAPE; M == 0 (all else valid): NF4DQ_OK, nothing launched; M*N*2, M*K*2 or
+ * packed_len reaching 2^31, N > 2^18, K > 2^24, more tickets (row blocks x column tiles) than
+ * the workspace header holds or a workspace need reaching 2^32 bytes: NF4DQ_ERR_TOO_LARGE.
+ * cfg NULL = the library's choice from (M, N, K, CU count) alone.  A cfg names kernel
+ * NF4DQ_GEMM_PF_DX (0 = the same) with
+ *   waves   waves per workgroup, 4 / 8: row blocks of 128 / 256 rows
+ *   depth   1
+ *   ksplit  slices of N, 1 .. min(N / 64, 16); ceil(N/64 / ksplit) steps per slice, so the last
+ *           slices may be short or empty
+ *   strips  0
+ * and never falls back: an invalid one, NF4DQ_GEMM_PF included, is NF4DQ_ERR_ARG.
+ * Workspace (nf4_gemm_bnb_pf_dx_workspace_bytes; 0 = none, one slice): nf4_gemm_bnb_mt's layout
+ * and contract -- the ticket header, then ksplit slabs of M * K floats, all zero between calls,
+ * shareable with the other fused entries on the same stream.  One ticket per (row block, column
+ * tile); the slice drawing the last one sums the slabs in slice order.  No workgroup waits for
+ * another.  The result is a function of the inputs and the cfg alone, and under one cfg a row's
+ * bits do not depend on M or on the other rows.
+ * Asynchronous on `hip_stream`; one launch; allocates nothing; capturable in a graph. */
+#define NF4DQ_GEMM_PF_DX 15
+size_t nf4_gemm_bnb_pf_dx_workspace_bytes(int64_t M, int64_t N, int64_t K, const nf4_gemm_cfg* cfg);
+int nf4_gemm_bnb_pf_dx(const void* g, int64_t M, const uint8_t* packed, int64_t packed_len,
+                       const uint8_t* absmax_q, int64_t nb, const float* code2,
+                       const float* absmax2, int64_t n2, const float* offset,
+                       int32_t blocksize, int32_t blocksize2,
+                       void* dx, int32_t out_dtype, int64_t N, int64_t K,
+                       void* workspace, size_t workspace_bytes, const nf4_gemm_cfg* cfg, void* hip_stream);
+int nf4_gemm_bnb_pf_dx_single(const void* g, int64_t M, const uint8_t* packed, int64_t packed_len,
+                              const float* absmax, int64_t nabs, int32_t blocksize,
+                              void* dx, int32_t out_dtype, int64_t N, int64_t K,
+                              void* workspace, size_t workspace_bytes, const nf4_gemm_cfg* cfg, void* hip_stream);
+
 /* The first half of a Llama-family MLP, `silu(gate(x)) * up(x)`, in bitsandbytes semantics for
  * 1..128 rows: ONE launch of the row-tiled family over the gate and the up weight, which share
  * x and the shape [I][K].  With dt = out_dtype (fp16 / bf16) and rn = round-to-nearest-even to dt,

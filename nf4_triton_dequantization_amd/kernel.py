@@ -810,8 +810,10 @@ def nf4_linear_bnb(x: torch.Tensor, module, bias: Optional[torch.Tensor] = None)
     tensors, more rows than ``GEMM_MT_ROUTED_M`` -- dequantizes with the HIP kernel and
     multiplies with torch, which autograd follows.  More rows than ``GEMM_MT_ROUTED_M`` within
     ``GEMM_PF_ROUTED_MIN_M .. GEMM_PF_ROUTED_MAX_M`` take ``nf4_linear_bnb_prefill``'s launch under
-    its rules; that range ships empty and is the caller's to open.  All paths use the same
-    weights and fp32 accumulation; the summation order differs, so the last bit of ``y`` may.
+    its rules; that range ships empty and is the caller's to open.  A call that records a gradient
+    for ``x`` with ``GEMM_DX_ROUTED_MIN_M .. GEMM_DX_ROUTED_MAX_M`` rows (shipped empty as well)
+    takes ``nf4_linear_bnb_autograd`` where ``nf4_linear_bnb_dx`` would launch.  All paths use the
+    same weights and fp32 accumulation; the summation order differs, so the last bit of ``y`` may.
     """
     weight = module.weight
     qs = weight.quant_state
@@ -823,6 +825,9 @@ def nf4_linear_bnb(x: torch.Tensor, module, bias: Optional[torch.Tensor] = None)
     if x.shape[-1] != K:
         raise RuntimeError(f"nf4_linear_bnb: x has {x.shape[-1]} features, weight expects {K}")
     lead, M = _lead_rows(x, K)
+    if (GEMM_DX_ROUTED_MIN_M <= M <= GEMM_DX_ROUTED_MAX_M and torch.is_grad_enabled() and x.requires_grad
+            and _bnb_dx_fusable(x, module, M)):
+        return nf4_linear_bnb_autograd(x, module, bias)
     if (M > GEMM_MT_ROUTED_M and GEMM_PF_ROUTED_MIN_M <= M <= GEMM_PF_ROUTED_MAX_M
             and _bnb_prefill_fusable(x, module, M)):
         return _bnb_prefill_launch(x, module, bias, None, lead, M)
@@ -853,6 +858,115 @@ def nf4_linear_bnb(x: torch.Tensor, module, bias: Optional[torch.Tensor] = None)
         _fused_call("nf4 fused bnb gemm", dev, getattr(L, entry), args,
                     L.nf4_gemm_bnb_mt_workspace_bytes if mt else L.nf4_gemm_bnb_workspace_bytes, (M, N, K, None))
         y = y.reshape(*lead, N)
+    if bias is not None:
+        y = y + bias.to(y.dtype)
+    return y
+
+
+# Rows at which nf4_linear_bnb, asked to record a gradient for x, takes nf4_linear_bnb_autograd (the
+# fused forward, nothing saved, nf4_linear_bnb_dx as the backward) in place of dequantize + matmul.
+# The range ships EMPTY: Linear4bit.forward and everything built on it behave as before
+# (profiles/gemm_dx/ has the measurements behind that decision).  A caller who fine-tunes and wants
+# no 16-bit weight copy kept from forward to backward and no host read of the offset sets
+# GEMM_DX_ROUTED_MAX_M = 8192, or calls nf4_linear_bnb_autograd itself.
+GEMM_DX_ROUTED_MIN_M = 1
+GEMM_DX_ROUTED_MAX_M = 0
+
+
+def _bnb_dx_fusable(grad_y: torch.Tensor, module, M: int) -> bool:
+    """_bnb_prefill_fusable's module rules at the input-gradient entry's shapes: 1..GEMM_PF_MAX_M
+    rows, K % 128 == 0, N % 64 == 0, blocksize 64, a 16-byte-aligned packed weight, and g, dx and
+    the packed weight within the entry's 32-bit byte offsets.  ``grad_y`` only has to be on the
+    weight's device (a gradient recorded for it -- a double backward -- takes the composite)."""
+    qs = module.weight.quant_state
+    qweight = module.weight.data
+    N, K = int(module.out_features), int(module.in_features)
+    return (qweight.device.type == "cuda" and grad_y.device == qweight.device and qs.dtype in (torch.float16, torch.bfloat16)
+            and 0 < M <= _lib.GEMM_PF_MAX_M and N >= 64 and N % 64 == 0 and K >= 128 and K % 128 == 0
+            and N <= 1 << 18 and K <= 1 << 24 and max(M * N * 2, M * K * 2, N * K // 2) < 1 << 31
+            and qweight.dtype == torch.uint8 and qweight.numel() == N * K // 2
+            and getattr(qs, "quant_type", None) == "nf4" and int(qs.blocksize) == 64 and _bnb_gemm_blocksizes(qs)
+            and qweight.data_ptr() % 16 == 0)
+
+
+def nf4_linear_bnb_dx(grad_y: torch.Tensor, module, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``grad_y @ W`` of shape ``[..., in_features]`` for a ``Linear4bit`` weight W in bitsandbytes
+    semantics: the input gradient of ``nf4_linear_bnb``, and -- the base weight being frozen -- the
+    layer's whole backward.
+
+    W is what ``dequantize_nf4_bnb(module)`` returns, bit for bit, but it is never written: ONE
+    launch (``nf4_gemm_bnb_pf_dx`` / ``nf4_gemm_bnb_pf_dx_single``) for 1 .. ``GEMM_PF_MAX_M``
+    (8192) rows stages the packed bytes in LDS, decodes each 64 x 128 weight tile once, transposed,
+    and multiplies it with a block of 128 or 256 rows of ``grad_y``, fp32 accumulation, one
+    rounding.  The offset is read on the device: no host read, capturable in a graph.  Taken on a
+    GPU for fp16 / bf16, nf4, a uint8 packed weight of N * K / 2 bytes that is 16-byte aligned,
+    blocksize 64, K % 128 == 0 and N % 64 == 0, with no gradient being recorded for ``grad_y``;
+    everything else -- CPU tensors, other block sizes, odd or too large shapes -- computes
+    ``grad_y.to(dtype) @ dequantize_nf4_bnb(module)``.  ``out=`` takes a contiguous tensor of the
+    result's shape and dtype.
+    """
+    qweight = module.weight.data
+    qs = module.weight.quant_state
+    dtype = qs.dtype
+    N, K = int(module.out_features), int(module.in_features)
+    if qweight.device.type == "cuda":
+        _same_device(grad_y, qweight)
+    if grad_y.shape[-1] != N:
+        raise RuntimeError(f"nf4_linear_bnb_dx: grad_y has {grad_y.shape[-1]} features, weight gives {N}")
+    lead, M = _lead_rows(grad_y, N)
+    if not _bnb_dx_fusable(grad_y, module, M) or (torch.is_grad_enabled() and grad_y.requires_grad):
+        return _into(out, grad_y.to(dtype) @ dequantize_nf4_bnb(module))
+    dev = qweight.device
+    _check_out("nf4_linear_bnb_dx", out, [*lead, K], dtype, dev)
+    direct = out is not None and out.data_ptr() % 8 == 0  # the launch stores into out itself
+    dx = out.view(M, K) if direct else torch.empty((M, K), dtype=dtype, device=dev)
+    gc = _rows(grad_y, N, dtype, True)
+    L = _lib.lib()
+    keep = []
+    entry = "nf4_gemm_bnb_pf_dx"
+    stats = _bnb_stats("nf4_linear_bnb_dx", qs, dev, keep)
+    if not _bnb_nested(qs):
+        entry += "_single"
+        stats = (stats[3], stats[4], stats[6])  # the single entries take (absmax, its count, blocksize) alone
+    args = (gc.data_ptr(), M, *_operand(qweight, None, keep), *stats, dx.data_ptr(), _dtype_code(dtype), N, K)
+    _fused_call("nf4 fused bnb input-gradient gemm", dev, getattr(L, entry), args, L.nf4_gemm_bnb_pf_dx_workspace_bytes,
+                (M, N, K, None))
+    return out if direct else _into(out, dx.reshape(*lead, K))
+
+
+class _LinearBnbFn(torch.autograd.Function):
+    """``nf4_linear_bnb`` without a bias as a differentiable function of ``x``: the forward is
+    ``nf4_linear_bnb`` itself with no gradient recorded (so its bits are that function's), NOTHING is
+    saved for the backward but the module reference -- no 16-bit weight, not ``x`` -- and the backward
+    is ``nf4_linear_bnb_dx``.  The weight has no gradient: it is frozen."""
+
+    @staticmethod
+    def forward(ctx, x, module):
+        ctx.module = module
+        ctx.x_dtype = x.dtype
+        with torch.no_grad():
+            return nf4_linear_bnb(x, module)
+
+    @staticmethod
+    def backward(ctx, grad):
+        with torch.no_grad():
+            dx = nf4_linear_bnb_dx(grad, ctx.module)
+        return dx.to(ctx.x_dtype), None
+
+
+def nf4_linear_bnb_autograd(x: torch.Tensor, module, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``nf4_linear_bnb`` that autograd follows without a 16-bit copy of the weight.
+
+    The forward is ``nf4_linear_bnb(x, module)`` with no gradient recorded -- the decode, row-tiled
+    or (where the caller opened that range) prefill launch by row count, dequantize + matmul outside
+    their rules -- and its bits are that function's.  Nothing is saved for the backward but the
+    module reference; the backward is ``nf4_linear_bnb_dx(grad, module)``, one fused launch under its
+    rules.  The bias is added in torch outside the function, so autograd follows it by itself.
+    ``x`` without ``requires_grad``, or with gradients disabled, is plain ``nf4_linear_bnb``.
+    """
+    if not (torch.is_grad_enabled() and x.requires_grad):
+        return nf4_linear_bnb(x, module, bias)
+    y = _LinearBnbFn.apply(x, module)
     if bias is not None:
         y = y + bias.to(y.dtype)
     return y
