@@ -557,6 +557,49 @@ int nf4_gemm_bnb_moe_rb(const void* x, const void* expert_ids, int64_t P, int32_
                         void* y, int32_t out_dtype, void* workspace, size_t workspace_bytes,
                         const nf4_gemm_cfg* cfg, void* hip_stream);
 
+/* nf4_gemm_bnb_moe for a prompt: the same product, descriptor, alignments, order of status codes
+ * and semantics as nf4_gemm_bnb_moe_rb for 1 <= P <= NF4DQ_MOE_PF_MAX_PAIRS (token, choice) pairs
+ * -- 8192 tokens at top-2 -- with no 16-bit copy of any expert's weight and no host read of the
+ * ids or the offsets.  ONE C call, three kernels on the stream:
+ *   1. a routing kernel (one workgroup) groups the pair indices by expert into perm[P] (ascending
+ *      within an expert; ids outside [0, experts) in one extra bucket) and cuts every bucket into
+ *      slots of at most BM = 32 * waves consecutive entries;
+ *   2. the GEMM, grid slots x column tiles x K slices: nf4_gemm_bnb_pf's workgroup (BM rows, 128
+ *      columns, one K slice, the step's 128 x 64 weights decoded once into LDS) on the slot's rows
+ *      of one expert, x gathered and y scattered through the slot's list.  The host launches
+ *      S = ceil(P / BM) + min(experts + 1, P) slots whatever the routing; unused ones return
+ *      before any load, an idle expert costs no weight traffic, and the pairs of an id outside
+ *      [0, experts) get rows of zero bits;
+ *   3. a kernel that puts the routing tables back to zero.
+ * Under one cfg a row's bits are those nf4_gemm_bnb_pf stores for that row with that expert's
+ * weight at the cfg of the same waves and ksplit; the result is a function of the inputs and the
+ * cfg alone (the order of perm is fixed by the ids: no atomic decides a position).
+ * Rules: nf4_gemm_bnb_moe_rb's, with N % 128 == 0 and N >= 128 (else NF4DQ_ERR_SHAPE);
+ * P > NF4DQ_MOE_PF_MAX_PAIRS: NF4DQ_ERR_SHAPE; P == 0: NF4DQ_OK, nothing launched;
+ * ceil(P / x_div)*K*2, P*N*2 or an expert's packed bytes reaching 2^31, ksplit > 1 with more
+ * tickets (S * N/128) than the workspace header holds or a workspace need reaching 2^32 bytes:
+ * NF4DQ_ERR_TOO_LARGE.
+ * cfg NULL = the library's choice from (P, experts, N, K, CU count) alone, never
+ * NF4DQ_ERR_TOO_LARGE for a shape the rules accept.  A cfg names kernel NF4DQ_GEMM_MOE_PF (0 =
+ * the same) with nf4_gemm_bnb_pf's fields (waves 4 / 8, depth 1, ksplit 1 .. min(K / 64, 16),
+ * strips 0) and never falls back: an invalid one, NF4DQ_GEMM_MOE_RB and NF4DQ_GEMM_PF included,
+ * is NF4DQ_ERR_ARG.
+ * Workspace (nf4_gemm_bnb_moe_pf_workspace_bytes; 0 only for a shape or cfg the entry rejects):
+ *   65792 (the ticket header) + (ksplit > 1 ? ksplit * P * N * 4 : 0) + tables,
+ *   tables = 16 * S + 4 * P + 4 * (experts + 1), rounded up to 16
+ * -- the slabs are indexed by position in perm; the tables are S slot entries, perm and the bucket
+ * counts.  Unlike the other fused entries it is needed for every call with P >= 1: a null or
+ * short one is NF4DQ_ERR_ARG.  ALL of it reads zero again when the call's work ends, so it is
+ * shareable with the other fused entries on the same stream.  No workgroup waits for another.
+ * Asynchronous on `hip_stream`; allocates nothing; capturable in a graph, and a replay follows
+ * whatever the router wrote into expert_ids since. */
+#define NF4DQ_MOE_PF_MAX_PAIRS 16384
+#define NF4DQ_GEMM_MOE_PF 16
+size_t nf4_gemm_bnb_moe_pf_workspace_bytes(int64_t P, const void* experts, const nf4_gemm_cfg* cfg);
+int nf4_gemm_bnb_moe_pf(const void* x, const void* expert_ids, int64_t P, int32_t x_div, const void* experts,
+                        void* y, int32_t out_dtype, void* workspace, size_t workspace_bytes,
+                        const nf4_gemm_cfg* cfg, void* hip_stream);
+
 /* The fused GEMM in bitsandbytes semantics for a prompt (prefill): nf4_gemm_bnb_mt's product,
  * argument lists, alignments and status codes for 1 <= M <= NF4DQ_GEMM_PF_MAX_M rows in ONE
  * launch, with no 16-bit copy of the weight and no host read of the offset.  W is bit for bit

@@ -1163,6 +1163,15 @@ def _moe_desc(experts) -> "_lib.MoeExperts":
 MOE_RB_ROUTED_MIN_P = 129
 MOE_RB_ROUTED_MAX_P = 1024
 
+# Pair counts above MOE_RB_ROUTED_MAX_P at which nf4_moe_linear_bnb takes the prompt launch
+# (nf4_gemm_bnb_moe_pf, whose domain is 1 .. MOE_PF_MAX_PAIRS) in place of the per-expert loop.  The
+# range ships EMPTY (MIN above MAX): what the launch costs against the loop in its best case is in
+# profiles/gemm_moe_pf/ (tools/bench_moe_pf.py), and the loop keeps the pair counts it had.  A caller
+# who wants a prompt through an MoE block captured in a graph -- no host read of the routing, no 16-bit
+# copy of an expert -- calls nf4_moe_linear_bnb_prefill, or sets MOE_PF_ROUTED_MAX_P = 16384.
+MOE_PF_ROUTED_MIN_P = 1
+MOE_PF_ROUTED_MAX_P = 0
+
 
 def nf4_moe_linear_bnb(x: torch.Tensor, experts, expert_ids: torch.Tensor,
                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1184,8 +1193,9 @@ def nf4_moe_linear_bnb(x: torch.Tensor, experts, expert_ids: torch.Tensor,
     <= MOE_RB_ROUTED_MAX_P``.  The ids and the offsets are
     read on the device, never by the host, so ``torch.cuda.graph`` captures the call and a replay
     follows whatever the router wrote into ``expert_ids`` since.  An expert without a pair costs
-    no weight traffic.  Everything else (more than ``MOE_RB_ROUTED_MAX_P`` pairs, CPU tensors, a
-    gradient for ``x``) takes the
+    no weight traffic.  More pairs than that take ``nf4_moe_linear_bnb_prefill``'s launch inside
+    ``MOE_PF_ROUTED_MIN_P .. MOE_PF_ROUTED_MAX_P``, which ships empty.  Everything else (more than
+    ``MOE_RB_ROUTED_MAX_P`` pairs, CPU tensors, a gradient for ``x``) takes the
     per-expert loop over ``nf4_linear_bnb(x[idx], experts.expert(e))``, which SYNCHRONISES with
     the host once per expert (it reads the routing back) and is therefore not capturable; autograd
     follows it to ``x``.  Both routes use the same weights and fp32 accumulation; the summation
@@ -1201,6 +1211,9 @@ def nf4_moe_linear_bnb(x: torch.Tensor, experts, expert_ids: torch.Tensor,
     P = T * k
     if P == 0:
         return out
+    if (P > MOE_RB_ROUTED_MAX_P and MOE_PF_ROUTED_MIN_P <= P <= MOE_PF_ROUTED_MAX_P
+            and _moe_pf_fusable(x, experts, P, x_div)):
+        return _moe_pf_call(x, experts, expert_ids, P, x_div, out)
     row_blocks = MOE_RB_ROUTED_MIN_P <= P <= MOE_RB_ROUTED_MAX_P
     if not _moe_fusable(x, experts, P, _lib.MOE_RB_MAX_PAIRS if row_blocks else _lib.MOE_MAX_PAIRS):
         return _moe_fallback(x3, experts, expert_ids, out)
@@ -1213,6 +1226,58 @@ def nf4_moe_linear_bnb(x: torch.Tensor, experts, expert_ids: torch.Tensor,
     _fused_call("nf4 fused moe gemm", dev, entry,
                 (xc.data_ptr(), ids.data_ptr(), P, x_div, dp, out.data_ptr(), _dtype_code(dtype)), size, (P, dp, None))
     return out
+
+
+def _moe_pf_fusable(x: torch.Tensor, experts, P: int, x_div: int) -> bool:
+    """nf4_gemm_bnb_moe_pf's rules (include/nf4_dequant.h): the expert entries' conditions up to its pair
+    bound, N in 128s, and the 2^31-byte bounds of x, y and one expert's packed weight."""
+    N, K = int(experts.out_features), int(experts.in_features)
+    return (_moe_fusable(x, experts, P, _lib.MOE_PF_MAX_PAIRS) and N % 128 == 0 and N <= 1 << 18 and K <= 1 << 24
+            and N * K // 2 < 1 << 31 and -(-P // x_div) * K * 2 < 1 << 31 and P * N * 2 < 1 << 31)
+
+
+def _moe_pf_call(x: torch.Tensor, experts, expert_ids: torch.Tensor, P: int, x_div: int, out: torch.Tensor) -> torch.Tensor:
+    """One nf4_gemm_bnb_moe_pf call into ``out`` ([T, k, N]); the caller has checked ``_moe_pf_fusable``."""
+    xc, ids = _moe_operands(x, expert_ids, experts.dtype)
+    desc = _moe_desc(experts)
+    L = _lib.lib()
+    dp = ctypes.cast(ctypes.pointer(desc), ctypes.c_void_p)
+    _fused_call("nf4 fused moe prefill gemm", experts.weight.data.device, L.nf4_gemm_bnb_moe_pf,
+                (xc.data_ptr(), ids.data_ptr(), P, x_div, dp, out.data_ptr(), _dtype_code(experts.dtype)),
+                L.nf4_gemm_bnb_moe_pf_workspace_bytes, (P, dp, None))
+    return out
+
+
+def nf4_moe_linear_bnb_prefill(x: torch.Tensor, experts, expert_ids: torch.Tensor,
+                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``nf4_moe_linear_bnb`` for a prompt: the same arguments, result and contract, served by
+    ``nf4_gemm_bnb_moe_pf`` for ``1 <= T*k <= MOE_PF_MAX_PAIRS`` pairs (8192 tokens at top-2).
+
+    One C call -- a routing kernel that groups the pairs by expert on the device, the prefill GEMM's
+    workgroups over each expert's rows, and a kernel that zeroes the routing tables -- plus at most
+    a cast of the ids to int32.  No expert's weight is dequantized to memory, the ids and the offsets
+    are never read by the host, and ``torch.cuda.graph`` captures the call: a replay follows
+    whatever the router wrote into ``expert_ids`` since.  An idle expert costs no weight traffic; a
+    pair whose id is outside ``0..E-1`` gets a row of zeros.
+
+    The entry is taken wherever its rules hold: GPU tensors, fp16 / bf16, N % 128 == 0, K % 128 ==
+    0, blocksize 64, no gradient being recorded for ``x``.  Everything else goes to
+    ``nf4_moe_linear_bnb`` (which itself takes this entry above ``MOE_RB_ROUTED_MAX_P`` pairs only
+    inside ``MOE_PF_ROUTED_MIN_P .. MOE_PF_ROUTED_MAX_P``, a range that ships empty).  The weights
+    and the fp32 accumulation are the same on every route; the summation order differs, so the last
+    bit of ``y`` may.
+    """
+    N = int(experts.out_features)
+    dtype = experts.dtype
+    dev = experts.weight.data.device
+    T, k, x_div, _ = _moe_args("nf4_moe_linear_bnb_prefill", x, experts, expert_ids)
+    P = T * k
+    if P == 0 or not _moe_pf_fusable(x, experts, P, x_div):
+        return nf4_moe_linear_bnb(x, experts, expert_ids, out)
+    _check_out("nf4_moe_linear_bnb_prefill", out, [T, k, N], dtype, dev)
+    if out is None:
+        out = torch.empty((T, k, N), dtype=dtype, device=dev)
+    return _moe_pf_call(x, experts, expert_ids, P, x_div, out)
 
 
 # Rows at which nf4_swiglu_bnb takes the fused launch (nf4_gemm_bnb_mt_swiglu): exactly those M
