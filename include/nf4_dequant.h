@@ -600,6 +600,39 @@ int nf4_gemm_bnb_moe_pf(const void* x, const void* expert_ids, int64_t P, int32_
                         void* y, int32_t out_dtype, void* workspace, size_t workspace_bytes,
                         const nf4_gemm_cfg* cfg, void* hip_stream);
 
+/* nf4_gemm_bnb_moe for decode, in 16-row slots: the same product, descriptor, rules, alignments,
+ * order of status codes and workspace contract for 1 <= P <= NF4DQ_MOE_MAX_PAIRS pairs in ONE
+ * launch, by a kernel of its own.  A slot is one (expert, block of 16 consecutive entries of that
+ * expert's ascending pair list), numbered in (expert, block) order; the grid is
+ * S = min(experts, P) + (P - min(experts, P)) / 16 slots x column tiles of 64 columns x K slices,
+ * fixed by the host whatever the routing.  Every workgroup finds its slot's expert and pairs from
+ * the P ids by ballots (no atomic decides a position); a slot past the used ones returns before
+ * any weight or statistics load, so an idle expert costs no such traffic.  K is split over the
+ * workgroup's 8 or 16 waves: each holds the slot's rows of x for its own 128-deep chunks in
+ * registers, walks the tile's four 16-column strips with a register ring of packed loads and
+ * decodes through a pair table in LDS (two weights per lookup) to the exact 16-bit weights.  The
+ * waves' partial tiles are summed in wave order, the K slices in slice order by the last arrival
+ * at the (slot, column tile)'s ticket: a row's bits depend on its x row, its expert and the cfg
+ * alone -- not on the batch around it, its slot or its place in the slot.  The summation order
+ * is not nf4_gemm_bnb_moe's, so the last bit may differ from that entry's.
+ * Differences from nf4_gemm_bnb_moe's rules: K / 128 > 512 (more than 16 K slices under every
+ * cfg) is NF4DQ_ERR_TOO_LARGE; the tickets are S * N/64.
+ * cfg NULL = the library's choice from (P, experts, N, K, CU count) alone.  A cfg names kernel
+ * NF4DQ_GEMM_MOE_DEC (0 = the same) with waves 8 / 16, depth 2 / 4 (strips of the tile in flight
+ * per wave), strips 1 / 2 (128-deep chunks per wave) and
+ * ksplit == ceil(K / 128 / (waves * strips)) <= 16, and never falls back: an invalid one,
+ * NF4DQ_GEMM_MOE included, is NF4DQ_ERR_ARG.
+ * Workspace (nf4_gemm_bnb_moe_dec_workspace_bytes; 0 = none, one K slice): nf4_gemm_bnb_moe's
+ * layout and contract -- the ticket header, then ksplit slabs of P * N floats indexed by pair, all
+ * zero between calls, shareable with the other fused entries on the same stream.  No workgroup
+ * waits for another; no float atomics.
+ * Asynchronous on `hip_stream`; one launch; allocates nothing; capturable in a graph. */
+#define NF4DQ_GEMM_MOE_DEC 17
+size_t nf4_gemm_bnb_moe_dec_workspace_bytes(int64_t P, const void* experts, const nf4_gemm_cfg* cfg);
+int nf4_gemm_bnb_moe_dec(const void* x, const void* expert_ids, int64_t P, int32_t x_div, const void* experts,
+                         void* y, int32_t out_dtype, void* workspace, size_t workspace_bytes,
+                         const nf4_gemm_cfg* cfg, void* hip_stream);
+
 /* The fused GEMM in bitsandbytes semantics for a prompt (prefill): nf4_gemm_bnb_mt's product,
  * argument lists, alignments and status codes for 1 <= M <= NF4DQ_GEMM_PF_MAX_M rows in ONE
  * launch, with no 16-bit copy of the weight and no host read of the offset.  W is bit for bit

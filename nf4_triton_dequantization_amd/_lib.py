@@ -87,6 +87,7 @@ GEMM_MOE_RB = 13  # the expert GEMM in row blocks, up to MOE_RB_MAX_PAIRS pairs 
 GEMM_PF = 14  # the prefill GEMM in row blocks of 128 / 256 rows (nf4_gemm_bnb_pf*: up to GEMM_PF_MAX_M rows); its own entries only
 GEMM_PF_DX = 15  # the input-gradient GEMM dx = g . W in row blocks of 128 / 256 rows (nf4_gemm_bnb_pf_dx*); its own entries only
 GEMM_MOE_PF = 16  # the expert GEMM for prompts, routed on the device (nf4_gemm_bnb_moe_pf: up to MOE_PF_MAX_PAIRS pairs); its own entry only
+GEMM_MOE_DEC = 17  # the expert GEMM for decode in 16-row slots (nf4_gemm_bnb_moe_dec: up to MOE_MAX_PAIRS pairs); its own entry only
 ACT_SILU = 0  # NF4DQ_ACT_SILU: the activation of nf4_gemm_bnb_mt_swiglu and nf4_gemm_bnb_moe_swiglu
 MOE_MAX_PAIRS = 128    # NF4DQ_MOE_MAX_PAIRS: (token, choice) pairs of one nf4_gemm_bnb_moe launch
 MOE_RB_MAX_PAIRS = 1024  # NF4DQ_MOE_RB_MAX_PAIRS: (token, choice) pairs of one nf4_gemm_bnb_moe_rb launch
@@ -229,6 +230,9 @@ SIGNATURES = {
     "nf4_gemm_bnb_moe_pf_workspace_bytes": (ctypes.c_size_t, [_I64, _P, ctypes.POINTER(GemmCfg)]),
     "nf4_gemm_bnb_moe_pf": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _I32, _P, ctypes.c_size_t,
                                            ctypes.POINTER(GemmCfg), _P]),
+    "nf4_gemm_bnb_moe_dec_workspace_bytes": (ctypes.c_size_t, [_I64, _P, ctypes.POINTER(GemmCfg)]),
+    "nf4_gemm_bnb_moe_dec": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _I32, _P, ctypes.c_size_t,
+                                            ctypes.POINTER(GemmCfg), _P]),
     # `gate_up`: const void* in the header, pointing at GemmBnbMat[2] (gate, up)
     "nf4_gemm_bnb_mt_swiglu_workspace_bytes": (ctypes.c_size_t, [_I64, _I64, _I64, ctypes.POINTER(GemmCfg)]),
     "nf4_gemm_bnb_mt_swiglu": (ctypes.c_int, [_P, _I64, _I64, _P, _I32, _I32, _P, _I32, _P, ctypes.c_size_t,

@@ -1172,6 +1172,15 @@ MOE_RB_ROUTED_MAX_P = 1024
 MOE_PF_ROUTED_MIN_P = 1
 MOE_PF_ROUTED_MAX_P = 0
 
+# Pair counts up to MOE_MAX_PAIRS at which nf4_moe_linear_bnb takes the slot launch
+# (nf4_gemm_bnb_moe_dec: 16-row slots, K over the waves, pair-table decode) in place of
+# nf4_gemm_bnb_moe.  The range ships EMPTY (MIN above MAX): the two launches sum in different orders,
+# so opening it changes the last bit of nf4_moe_linear_bnb's results.  What either costs is in
+# profiles/gemm_moe_dec/ (tools/bench_moe_dec.py).  A caller who wants the slot launch calls
+# nf4_moe_linear_bnb_decode, or sets MOE_DEC_ROUTED_MAX_P = 128.
+MOE_DEC_ROUTED_MIN_P = 1
+MOE_DEC_ROUTED_MAX_P = 0
+
 
 def nf4_moe_linear_bnb(x: torch.Tensor, experts, expert_ids: torch.Tensor,
                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1194,7 +1203,9 @@ def nf4_moe_linear_bnb(x: torch.Tensor, experts, expert_ids: torch.Tensor,
     read on the device, never by the host, so ``torch.cuda.graph`` captures the call and a replay
     follows whatever the router wrote into ``expert_ids`` since.  An expert without a pair costs
     no weight traffic.  More pairs than that take ``nf4_moe_linear_bnb_prefill``'s launch inside
-    ``MOE_PF_ROUTED_MIN_P .. MOE_PF_ROUTED_MAX_P``, which ships empty.  Everything else (more than
+    ``MOE_PF_ROUTED_MIN_P .. MOE_PF_ROUTED_MAX_P``, which ships empty; up to ``MOE_MAX_PAIRS`` pairs
+    inside ``MOE_DEC_ROUTED_MIN_P .. MOE_DEC_ROUTED_MAX_P``, which ships empty too, the launch is
+    ``nf4_moe_linear_bnb_decode``'s (``nf4_gemm_bnb_moe_dec``).  Everything else (more than
     ``MOE_RB_ROUTED_MAX_P`` pairs, CPU tensors, a gradient for ``x``) takes the
     per-expert loop over ``nf4_linear_bnb(x[idx], experts.expert(e))``, which SYNCHRONISES with
     the host once per expert (it reads the routing back) and is therefore not capturable; autograd
@@ -1214,6 +1225,9 @@ def nf4_moe_linear_bnb(x: torch.Tensor, experts, expert_ids: torch.Tensor,
     if (P > MOE_RB_ROUTED_MAX_P and MOE_PF_ROUTED_MIN_P <= P <= MOE_PF_ROUTED_MAX_P
             and _moe_pf_fusable(x, experts, P, x_div)):
         return _moe_pf_call(x, experts, expert_ids, P, x_div, out)
+    if (P <= _lib.MOE_MAX_PAIRS and MOE_DEC_ROUTED_MIN_P <= P <= MOE_DEC_ROUTED_MAX_P
+            and _moe_dec_fusable(x, experts, P)):
+        return _moe_dec_call(x, experts, expert_ids, P, x_div, out)
     row_blocks = MOE_RB_ROUTED_MIN_P <= P <= MOE_RB_ROUTED_MAX_P
     if not _moe_fusable(x, experts, P, _lib.MOE_RB_MAX_PAIRS if row_blocks else _lib.MOE_MAX_PAIRS):
         return _moe_fallback(x3, experts, expert_ids, out)
@@ -1278,6 +1292,56 @@ def nf4_moe_linear_bnb_prefill(x: torch.Tensor, experts, expert_ids: torch.Tenso
     if out is None:
         out = torch.empty((T, k, N), dtype=dtype, device=dev)
     return _moe_pf_call(x, experts, expert_ids, P, x_div, out)
+
+
+def _moe_dec_fusable(x: torch.Tensor, experts, P: int) -> bool:
+    """nf4_gemm_bnb_moe_dec's rules (include/nf4_dequant.h): nf4_gemm_bnb_moe's, and K within 16 K slices."""
+    return _moe_fusable(x, experts, P, _lib.MOE_MAX_PAIRS) and int(experts.in_features) // 128 <= 512
+
+
+def _moe_dec_call(x: torch.Tensor, experts, expert_ids: torch.Tensor, P: int, x_div: int, out: torch.Tensor) -> torch.Tensor:
+    """One nf4_gemm_bnb_moe_dec launch into ``out`` ([T, k, N]); the caller has checked ``_moe_dec_fusable``."""
+    xc, ids = _moe_operands(x, expert_ids, experts.dtype)
+    desc = _moe_desc(experts)
+    L = _lib.lib()
+    dp = ctypes.cast(ctypes.pointer(desc), ctypes.c_void_p)
+    _fused_call("nf4 fused moe decode gemm", experts.weight.data.device, L.nf4_gemm_bnb_moe_dec,
+                (xc.data_ptr(), ids.data_ptr(), P, x_div, dp, out.data_ptr(), _dtype_code(experts.dtype)),
+                L.nf4_gemm_bnb_moe_dec_workspace_bytes, (P, dp, None))
+    return out
+
+
+def nf4_moe_linear_bnb_decode(x: torch.Tensor, experts, expert_ids: torch.Tensor,
+                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``nf4_moe_linear_bnb`` for a decode step: the same arguments, result and contract, served by
+    ``nf4_gemm_bnb_moe_dec`` for ``1 <= T*k <= MOE_MAX_PAIRS`` pairs.
+
+    ONE launch plus at most a cast of the ids to int32.  Its workgroups each take one slot -- 16
+    consecutive pairs of one expert's ascending list -- found from the ids on the device, split K
+    over 8 or 16 waves that keep their rows of x in registers, and decode two weights per LDS lookup
+    through a pair table.  The ids and the offsets are never read by the host, so
+    ``torch.cuda.graph`` captures the call and a replay follows whatever the router wrote into
+    ``expert_ids`` since.  An idle expert costs no weight traffic; a pair whose id is outside
+    ``0..E-1`` gets a row of zeros.  A row's bits depend on its row of x, its expert and the launch's
+    configuration alone, not on the batch around it.
+
+    The entry is taken wherever ``nf4_moe_linear_bnb``'s fused-route conditions hold at up to
+    ``MOE_MAX_PAIRS`` pairs (and K <= 65536).  Everything else goes to ``nf4_moe_linear_bnb`` (which
+    itself takes this entry only inside ``MOE_DEC_ROUTED_MIN_P .. MOE_DEC_ROUTED_MAX_P``, a range
+    that ships empty).  The weights and the fp32 accumulation are the same on every route; the
+    summation order differs, so the last bit of ``y`` may.
+    """
+    N = int(experts.out_features)
+    dtype = experts.dtype
+    dev = experts.weight.data.device
+    T, k, x_div, _ = _moe_args("nf4_moe_linear_bnb_decode", x, experts, expert_ids)
+    P = T * k
+    if P == 0 or not _moe_dec_fusable(x, experts, P):
+        return nf4_moe_linear_bnb(x, experts, expert_ids, out)
+    _check_out("nf4_moe_linear_bnb_decode", out, [T, k, N], dtype, dev)
+    if out is None:
+        out = torch.empty((T, k, N), dtype=dtype, device=dev)
+    return _moe_dec_call(x, experts, expert_ids, P, x_div, out)
 
 
 # Rows at which nf4_swiglu_bnb takes the fused launch (nf4_gemm_bnb_mt_swiglu): exactly those M
